@@ -5,8 +5,10 @@ A "step" is one pass of the hot path over one batch of synthetic input: one `Com
 (= DlogGroupExt::vartime_multiscalar_mul, /root/reference benches/commit.rs:120-124) over uniformly random BN254
 scalars, commitment key resident in HBM, scalars resident in HBM when the timed region starts.
 
-  N = 1 (default)  BASELINE.json configs[1]: 2^20 pairs on one GPU.  The same JSON line also carries the other
-                   headline-adjacent numbers, each cross-checked against the CPU oracle: `incl_h2d` (scalars in pageable
+  N = 1 (default)  BASELINE.json configs[1]: 2^20 pairs on one GPU.  A plain run sets up, warms up, times the steps and
+                   prints the headline line.  With --full the same JSON line also carries `cpu_baseline` (the CPU oracle
+                   on the same inputs, with the bit-exact check) and the other headline-adjacent numbers, each
+                   cross-checked against the CPU oracle: `incl_h2d` (scalars in pageable
                    host memory), `trait_form` (the reference's slice-form signature over pageable
                    Montgomery-layout host arrays: the slice cache path), `anchor_2p24_single_gpu` (the N = 1 point of the
                    configs[2] curve), `prove_step_replay_ms` (configs[3] shapes incl. the six SpMVs) and
@@ -19,6 +21,8 @@ scalars, commitment key resident in HBM, scalars resident in HBM when the timed 
                    (--log2n X with N > 1 gives the old weak-scaling run, 2^X pairs per GPU.)
 
   python bench.py                      # 1 GPU, 2^20 pairs, prints ONE JSON line
+  python bench.py --full               # the same line with cpu_baseline and every extra block
+  python bench.py --dump-outputs DIR   # also writes the last timed step's result as DIR/msm_xy.npy, DIR/msm_is_inf.npy
   python bench.py --log2n 24 --no-extras   # the single-GPU anchor of the 2^24 curve on its own
   python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port P \
          bench.py --gpus 8 --steps K --warmup W
@@ -124,7 +128,7 @@ def main():
                     help="force the fixed-total (strong-scaling) sharding even at N = 1 (exercises the N > 1 code path on one GPU "
                          "together with NMX_BENCH_FORCE_DIST=1)")
     ap.add_argument("--no-extras", action="store_true",
-                    help="N = 1 headline run: skip incl_h2d / trait_form / 2^24 anchor / prove_step / HyperKZG replays")
+                    help="N = 1 headline run with --full: skip incl_h2d / trait_form / 2^24 anchor / prove_step / HyperKZG replays")
     ap.add_argument("--curve", type=int, default=0, help="0 bn254_g1 (headline), 1 grumpkin, 2 pallas, 3 vesta")
     ap.add_argument("--dist", default="random", help="scalar distribution: random | u1 | u10 | u16 | u32 | u64")
     ap.add_argument("--no-cpu-baseline", action="store_true")
@@ -148,7 +152,18 @@ def main():
     ap.add_argument("--workload", default="msm", choices=["msm", "axpy", "cross_term", "bind", "sumcheck3", "round3", "quad_prod", "lincomb8", "horner", "mle_eval", "spmv", "prove_step_replay", "hyperkzg_replay", "spartan_replay", "compressed_snark_replay", "ipa_replay"],
                     help="msm = the headline (default); the others time one HBM-bound field-vector kernel of "
                          "SURVEY.md 8(f) at 2^log2n elements per GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="msm: also run what the headline figure does not need -- the CPU oracle baseline with its bit-exact check and "
+                         "(N = 1, 2^20, BN254, random) the extra blocks: incl_h2d, trait_form, commit_rs_sets, the 2^24 anchor, the "
+                         "replays and the field-vector rooflines (--no-cpu-baseline / --no-extras still skip them)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32 / float64; "
+                         "256-bit values as 16-bit limbs, exact); --workload msm only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "msm":
+        ap.error(f"--dump-outputs: not implemented for --workload {args.workload}")
     strong = (args.gpus > 1 and args.log2n is None) or args.strong      # configs[2] as written: fixed total, contiguous shards
     args.inproc_log2n = args.total_log2n if strong else args.log2n     # in-process mode (below): pairs in total
     if args.log2n is None:
@@ -261,6 +276,8 @@ def main():
         tmax = torch.tensor([dt], dtype=torch.float64, device="cuda")
         dist.all_reduce(tmax, op=dist.ReduceOp.MAX)
         dt = float(tmax.item())
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, point_arrays("msm", result))
 
     out = None
     MADS_PER_MADD = MADS_PER_MADD_BY_CURVE[cid]
@@ -352,9 +369,9 @@ def main():
         out["reduction_tree"] = "one launch per level (NMX_TUNE_NO_TREE_FUSE=1)" if os.environ.get("NMX_TUNE_NO_TREE_FUSE") == "1" else "fused levels"
         if multi:
             out["combine_ms"] = round(combine_s[0] / max(args.steps, 1) * 1e3, 4)
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cid, ck, host_sc[(args.steps - 1) & 1], n, result)
-        if world == 1 and not force_dist and not args.no_extras and args.log2n == 20 and args.dist == "random" and cid == 0:
+        if world == 1 and args.full and not force_dist and not args.no_extras and args.log2n == 20 and args.dist == "random" and cid == 0:
             extras(out, args, torch, L, ck, host_sc[0], dev_sc[0])
     ck.close()
     emit(out if rank == 0 else None, multi, dist)
@@ -439,6 +456,8 @@ def inprocess_multi(args, torch):
         torch.cuda.synchronize(d)
     dt = time.perf_counter() - t0
     L.nmx_set_profiling(0)
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, point_arrays("msm", res))
     sharded_calls = _lib.stats()[_lib.STAT_SHARDED_CALLS] - before
     last = sets[(args.steps - 1) & 1]
     name = nova_amd.CURVE_NAMES[cid]
@@ -492,7 +511,7 @@ def inprocess_multi(args, torch):
                                    "stream); the MSM is integer-VALU-bound, not HBM-bound (DESIGN.md section 5)"}
     # contrast: the same call with ONE HBM array on GPU 0 (NMX_SCALARS_DEVICE), every other shard pulling its slice over xGMI
     # inside the call -- what round 3 timed
-    if k > 1 and not args.no_extras:
+    if k > 1 and args.full and not args.no_extras:
         try:
             one = torch.cat([p.to("cuda:0") for p in last]).contiguous()
             torch.cuda.synchronize(0)
@@ -509,7 +528,7 @@ def inprocess_multi(args, torch):
         except (RuntimeError, nova_amd.NmxError) as e:
             out["scalars_on_gpu0"] = {"error": str(e)}
     # the CPU oracle at FULL size on the last timed input: the baseline and the bit-exact check in one pass
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         from oracle import cref
         threads = effective_cpus()
         cref.set_threads(threads)
@@ -904,6 +923,21 @@ def extras(out, args, torch, L, ck, host_scalars, dev_scalars):
 def util_modulus(fid):
     from oracle import pyref as R
     return [R.BN254_Q, R.BN254_R, R.PALLAS_P, R.PALLAS_Q][fid]
+
+
+def dump_outputs(d, arrays):
+    """--dump-outputs: every {name: float32 / float64 array} as d/<name>.npy."""
+    os.makedirs(d, exist_ok=True)
+    for name, a in arrays.items():
+        assert a.dtype in (np.float32, np.float64), (name, a.dtype)
+        np.save(os.path.join(d, name + ".npy"), a)
+
+
+def point_arrays(name, p):
+    """The affine point a caller receives: canonical x, y as 2 x 16 little-endian 16-bit limbs (exact in float64), and
+    the identity flag."""
+    xy = np.frombuffer(bytes(p.xy), dtype="<u2").reshape(2, 16).astype(np.float64)
+    return {f"{name}_xy": xy, f"{name}_is_inf": np.array([float(bool(p.is_inf))])}
 
 
 def emit(result, world_or_dist, dist):

@@ -13,7 +13,7 @@ timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -5
 echo "== pytest gpu"
 timeout 1500 python -m pytest tests -x -q -m gpu 2>&1 | tail -25 | tee "$OUT/pytest_gpu.txt"
 echo "== bench"
-timeout 600 python bench.py --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"
+timeout 600 python bench.py --full --steps 10 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"; cat "$OUT/bench.json"; tail -5 "$OUT/bench.err"
 echo "== host-scalar (PCIe-inclusive) rate"
 timeout 300 python - <<'PY' | tee "$OUT/pcie_inclusive.txt"
 import time, numpy as np, nova_amd

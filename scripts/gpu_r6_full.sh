@@ -6,7 +6,7 @@ OUT=gpurun_out/r6full
 mkdir -p "$OUT"
 ( time timeout 3000 python -m pytest tests -x -q -m gpu 2>&1 | tail -8 ) 2>&1 | tee "$OUT/pytest_gpu.txt"
 timeout 600 python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | tail -3 | tee "$OUT/smoke.txt"
-( time timeout 1200 python bench.py > "$OUT/bench_default_line.json" 2> "$OUT/bench.err" ) 2>&1 | tail -4 | tee "$OUT/bench_time.txt"
+( time timeout 1200 python bench.py --full > "$OUT/bench_default_line.json" 2> "$OUT/bench.err" ) 2>&1 | tail -4 | tee "$OUT/bench_time.txt"
 tail -3 "$OUT/bench.err" | grep -v amdgpu.ids
 python - "$OUT/bench_default_line.json" <<'PY'
 import json, sys

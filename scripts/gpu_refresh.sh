@@ -2,7 +2,7 @@
 # regenerate the bench JSONs kept under profiles/r01_msm_2p20 and profiles/r01_fieldvec with the current build
 set -u
 O=gpurun_out/refresh; mkdir -p $O
-b() { timeout 300 python bench.py "$@" 2>/dev/null | tail -1; }
+b() { timeout 300 python bench.py --full "$@" 2>/dev/null | tail -1; }
 for d in random u1 u10 u16 u64 equal zero_rm1 pm_small; do b --dist $d --no-cpu-baseline --steps 20 > $O/dist_$d.json; done
 for l in 10 12 13 14 16 22 24; do b --log2n $l --no-cpu-baseline --steps 20 > $O/bench_2p${l}_single_gpu.json; done
 for it in 1024 65536; do b --workload prove_step_replay --iters $it --steps 20 > $O/replay_$it.json; done
