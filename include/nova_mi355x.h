@@ -524,6 +524,32 @@ int nmx_r1cs_cross_term(uint64_t A, uint64_t B, uint64_t C, const void* z1, cons
                         const void* u, uint32_t flags, void* out);
 int nmx_nifs_fold(int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e, const void* r,
                   uint32_t flags, void* w, void* e);
+/* R1CSShape::is_sat_relaxed / is_sat (src/r1cs/mod.rs:474-574) as ONE call -- what RecursiveSNARK::verify runs three of under
+ * rayon::join (src/nova/mod.rs:637-660), and what `debug_assert!(shape.is_sat_relaxed(..))` needs on the prover's side with the
+ * witness already in HBM.  z = [W, u, X]; on every row (A z)(B z) == u (C z) + E (strict form: == C z, u = 1, no E), decided ON THE
+ * DEVICE: A z, B z, C z and the residual never reach HBM, a satisfied instance writes nothing at all; and
+ * commit(ck, W, r_W) == comm_W, commit(ck, E, r_E) == comm_E, the two commitments begun before the equation pass (the machinery of
+ * nmx_commit_begin) so that the pass runs under them.
+ *   A, B, C     matrices of one shape and field (nmx_spmv_register); the field must be the scalar field of the key's curve (NMX_E_ARG)
+ *   E, u        both NULL: is_sat (n_e, r_E, comm_E_* ignored); both given: is_sat_relaxed; one of the two NULL: NMX_E_ARG
+ *   lengths     n_w + 1 + n_io != cols or n_e != rows: NMX_E_ARG, the message says which (the reference's W.len() != num_vars,
+ *               X.len() != num_io, E.len() != num_cons, mod.rs:489-494, 540-545); n_w or n_e beyond the key: NMX_E_HANDLE (as nmx_commit);
+ *               unknown matrix / key handle: NMX_E_HANDLE.  All of it is checked before anything is launched.
+ *   ck_handle   0: the equation only (no commitments; r_*, h, comm_* ignored, the COMM bits stay clear)
+ *   flags       NMX_SCALARS_DEVICE: W and E are HBM pointers (otherwise host arrays, uploaded for the call -- a proof that arrives from a
+ *               peer is in host memory); NMX_SCALARS_MONT: W, E, u, X, r_W, r_E are Montgomery limbs; NMX_BASES_MONT: h_xy64 AND the two
+ *               expected commitments are.  u, X, r_*, h_xy64, comm_* are always host pointers; comm_*_is_inf != 0: the expected
+ *               commitment is the identity (its bytes are not read).  Any other flag: NMX_E_ARG.
+ *   result      NMX_OK whenever the check RAN; the answer is *verdict: 0 = satisfied, else the OR of NMX_UNSAT_* -- every condition is
+ *               evaluated (the reference reports the equation first, mod.rs:516-527: that ordering is the caller's to apply).
+ *               *bad_rows / *first_bad_row (may be NULL): number of violated rows and the lowest one, 2^64 - 1 when there is none.
+ *               On an error nothing is written.  Synchronous, ordered behind the calling thread's NMX_ASYNC calls like every
+ *               synchronous call; keys sharded over several devices work as they do for nmx_commit. */
+enum { NMX_UNSAT_EQ = 1u << 0, NMX_UNSAT_COMM_W = 1u << 1, NMX_UNSAT_COMM_E = 1u << 2 };
+int nmx_r1cs_is_sat(uint64_t A, uint64_t B, uint64_t C, uint64_t ck_handle, const void* W, size_t n_w, const void* E, size_t n_e,
+                    const void* u, const void* X, size_t n_io, const void* r_W, const void* r_E, const void* h_xy64,
+                    const void* comm_W_xy64, int comm_W_is_inf, const void* comm_E_xy64, int comm_E_is_inf, uint32_t flags,
+                    uint32_t* verdict, uint64_t* bad_rows, uint64_t* first_bad_row);
 /* compute_eval_table_sparse's product (src/spartan/mod.rs:497-533: `M_evals[col] += rx[row] * val` over every entry), i.e.
  * out[cols] = M^T * x with x_len == rows -- Spartan's inner sum-check needs it for A, B and C with x = eq(r_x, .)
  * (src/spartan/snark.rs:181-190).  The transposed form (CSC cut into lanes; a column as long as the constant-one column of an

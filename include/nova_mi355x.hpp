@@ -436,6 +436,37 @@ inline void multiply_vec3(const uint64_t mats[3], bool transposed, const void* x
 inline void r1cs_cross_term(const uint64_t mats[3], const void* z, size_t z_len, const void* e, const Scalar& u, void* out) {
   check(nmx_r1cs_cross_term(mats[0], mats[1], mats[2], z, nullptr, z_len, e, u.data(), kAsync, out));
 }
+// R1CSShape::is_sat / is_sat_relaxed (r1cs/mod.rs:474-574; the three checks of RecursiveSNARK::verify, nova/mod.rs:637-660) as one
+// call each: the equation decided on the device, the commitments beside it.  W (n_w elements) and E (n_e) are HBM pointers, or host
+// arrays with device = false (a proof received from a peer); X is a host vector; comm_W / comm_E in the key's form (Montgomery when
+// ck.mont(), like ck.h()).  ck == nullptr: the equation only (the prover-side debug_assert!).
+struct SatResult {
+  uint32_t verdict = 0;  // OR of NMX_UNSAT_*
+  uint64_t bad_rows = 0, first_bad_row = ~0ull;
+  bool ok() const { return verdict == 0; }
+  bool eq_ok() const { return !(verdict & NMX_UNSAT_EQ); }
+  bool comm_W_ok() const { return !(verdict & NMX_UNSAT_COMM_W); }
+  bool comm_E_ok() const { return !(verdict & NMX_UNSAT_COMM_E); }
+};
+inline SatResult r1cs_is_sat_relaxed(const uint64_t mats[3], const CommitmentKey* ck, const void* W, size_t n_w, const void* E, size_t n_e,
+                                     const Scalar& u, const std::vector<Scalar>& X, const Point& comm_W, const Point& comm_E,
+                                     const Scalar& r_W = Scalar{}, const Scalar& r_E = Scalar{}, bool device = true, bool mont = false) {
+  SatResult s;
+  const uint32_t flags = (device ? kDev : 0u) | (mont ? NMX_SCALARS_MONT : 0u) | ((ck && ck->mont()) ? NMX_BASES_MONT : 0u);
+  check(nmx_r1cs_is_sat(mats[0], mats[1], mats[2], ck ? ck->handle() : 0, W, n_w, E, n_e, u.data(), X.empty() ? nullptr : X[0].data(), X.size(),
+                        r_W.data(), r_E.data(), ck ? ck->h().data() : nullptr, comm_W.xy.data(), comm_W.is_inf ? 1 : 0, comm_E.xy.data(),
+                        comm_E.is_inf ? 1 : 0, flags, &s.verdict, &s.bad_rows, &s.first_bad_row));
+  return s;
+}
+inline SatResult r1cs_is_sat(const uint64_t mats[3], const CommitmentKey* ck, const void* W, size_t n_w, const std::vector<Scalar>& X,
+                             const Point& comm_W, const Scalar& r_W = Scalar{}, bool device = true, bool mont = false) {
+  SatResult s;
+  const uint32_t flags = (device ? kDev : 0u) | (mont ? NMX_SCALARS_MONT : 0u) | ((ck && ck->mont()) ? NMX_BASES_MONT : 0u);
+  check(nmx_r1cs_is_sat(mats[0], mats[1], mats[2], ck ? ck->handle() : 0, W, n_w, nullptr, 0, nullptr, X.empty() ? nullptr : X[0].data(), X.size(),
+                        r_W.data(), nullptr, ck ? ck->h().data() : nullptr, comm_W.xy.data(), comm_W.is_inf ? 1 : 0, nullptr, 0, flags,
+                        &s.verdict, &s.bad_rows, &s.first_bad_row));
+  return s;
+}
 inline Scalar mle_evaluate(int field, const void* z, size_t len, const std::vector<Scalar>& r) {
   Scalar out;
   check(nmx_mle_evaluate(field, z, len, r.data(), r.size(), kDev, out.data()));

@@ -22,6 +22,7 @@ DEVICES_OVERSUBSCRIBE = 1
 E_ARG, E_NO_DEVICE, E_HIP, E_SCALAR_RANGE, E_SMALL_RANGE, E_HANDLE, E_TOO_LARGE = -1, -2, -3, -4, -5, -6, -7
 E_IO, E_FORMAT, E_POINT, E_ZERO = -8, -9, -10, -11
 BITS_AUTO = 0xFFFFFFFF
+UNSAT_EQ, UNSAT_COMM_W, UNSAT_COMM_E = 1, 2, 4  # nmx_r1cs_is_sat's verdict bits
 
 # nmx_transcript_fn: (ctx, round polynomial coefficients, how many, challenge out) -> 0
 TRANSCRIPT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t,
@@ -104,6 +105,8 @@ def lib():
     L.nmx_spmv_unregister.argtypes = [u64]
     L.nmx_spmv_apply.argtypes = [u64, vp, sz, u32, vp]
     L.nmx_r1cs_cross_term.argtypes = [u64, u64, u64, vp, vp, sz, vp, vp, u32, vp]
+    L.nmx_r1cs_is_sat.argtypes = [u64, u64, u64, u64, vp, sz, vp, sz, vp, vp, sz, vp, vp, vp, vp, i, vp, i, u32,
+                                  ctypes.POINTER(u32), ctypes.POINTER(u64), ctypes.POINTER(u64)]
     L.nmx_nifs_fold.argtypes = [i, vp, vp, sz, vp, vp, sz, vp, u32, vp, vp]
     L.nmx_spmv_apply_pair.argtypes = [u64, vp, vp, sz, u32, vp, vp]
     L.nmx_poly_fold_chain.argtypes = [ctypes.c_int, vp, sz, vp, sz, u32, vp]

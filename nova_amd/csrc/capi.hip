@@ -1912,37 +1912,41 @@ static void drain_pending_commits() {
   }
   gone.clear();  // ~PoolFuture waits; results and errors of unfinished tickets are dropped
 }
+// the commitment behind a ticket, started: leases its context on the CALLING thread and hands the work to a pool worker
+static std::shared_ptr<PendingCommit> start_commit(BaseRef bs, const void* v, size_t n, const void* h_xy64, const void* r, uint32_t flags) {
+  require(n <= bs->n, NMX_E_HANDLE, "ck shorter than v");
+  std::array<uint8_t, 64> hb;
+  std::array<uint8_t, 32> rb;
+  memcpy(hb.data(), h_xy64, 64);
+  memcpy(rb.data(), r, 32);
+  const MsmCall mc = field_call(v, flags);
+  auto lease = std::make_shared<CtxLease>();  // on the calling thread: behind its stream-ordered calls
+  // The worker must see the caller's pending NMX_ASYNC mark as well (thread-local): a sharded key leases one context per shard
+  // INSIDE the job (key_msm -> run_on_parts reads async_pending() of the thread it runs on), and those leases have to wait for
+  // the caller's asynchronous producer just as the lease above does (capi.hip:1914).
+  Ctx* const pend = async_pending();
+  const uint64_t pend_epoch = t_async_epoch;
+  auto pc = std::make_shared<PendingCommit>();
+  pc->flags = flags;
+  pc->fut = PoolFuture<PendingCommit::Res>([bs, mc, n, hb, rb, flags, lease, pend, pend_epoch]() mutable {
+    std::shared_ptr<CtxLease> L = std::move(lease);  // handed back when the job ends, whatever happens
+    struct Restore {  // the worker's own mark comes back when the job ends (as run_on_parts' helper threads do)
+      Ctx* v;
+      uint64_t e;
+      ~Restore() { t_async_ctx = v, t_async_epoch = e; }
+    } restore{t_async_ctx, t_async_epoch};
+    t_async_ctx = pend, t_async_epoch = pend_epoch;
+    HIPCHK(hipSetDevice(hip_device_of(L->c->dev)));  // (the device is per host thread)
+    PendingCommit::Res res;
+    commit_impl(*L, *bs, mc, n, hb.data(), rb.data(), flags, res.out.data(), &res.inf);
+    return res;
+  });
+  return pc;
+}
 int nmx_commit_begin(uint64_t ck_handle, const void* v, size_t n, const void* h_xy64, const void* r, uint32_t flags, uint64_t* ticket) {
   return guarded([&] {
     require(ticket && (v || n == 0) && h_xy64 && r, NMX_E_ARG, "null argument");
-    BaseRef bs = lookup(ck_handle);
-    require(n <= bs->n, NMX_E_HANDLE, "ck shorter than v");
-    std::array<uint8_t, 64> hb;
-    std::array<uint8_t, 32> rb;
-    memcpy(hb.data(), h_xy64, 64);
-    memcpy(rb.data(), r, 32);
-    const MsmCall mc = field_call(v, flags);
-    auto lease = std::make_shared<CtxLease>();  // on the calling thread: behind its stream-ordered calls
-    // The worker must see the caller's pending NMX_ASYNC mark as well (thread-local): a sharded key leases one context per shard
-    // INSIDE the job (key_msm -> run_on_parts reads async_pending() of the thread it runs on), and those leases have to wait for
-    // the caller's asynchronous producer just as the lease above does (capi.hip:1914).
-    Ctx* const pend = async_pending();
-    const uint64_t pend_epoch = t_async_epoch;
-    auto pc = std::make_shared<PendingCommit>();
-    pc->flags = flags;
-    pc->fut = PoolFuture<PendingCommit::Res>([bs, mc, n, hb, rb, flags, lease, pend, pend_epoch]() mutable {
-      std::shared_ptr<CtxLease> L = std::move(lease);  // handed back when the job ends, whatever happens
-      struct Restore {  // the worker's own mark comes back when the job ends (as run_on_parts' helper threads do)
-        Ctx* v;
-        uint64_t e;
-        ~Restore() { t_async_ctx = v, t_async_epoch = e; }
-      } restore{t_async_ctx, t_async_epoch};
-      t_async_ctx = pend, t_async_epoch = pend_epoch;
-      HIPCHK(hipSetDevice(hip_device_of(L->c->dev)));  // (the device is per host thread)
-      PendingCommit::Res res;
-      commit_impl(*L, *bs, mc, n, hb.data(), rb.data(), flags, res.out.data(), &res.inf);
-      return res;
-    });
+    auto pc = start_commit(lookup(ck_handle), v, n, h_xy64, r, flags);
     std::lock_guard<std::mutex> lk(g_pend_mu);
     const uint64_t t = g_next_ticket++;
     pending_commits()[t] = std::move(pc);
@@ -2851,6 +2855,86 @@ int nmx_r1cs_cross_term(uint64_t hA, uint64_t hB, uint64_t hC, const void* z1, c
     const uint32_t* dt[3] = {sp[0]->data, sp[1]->data, sp[2]->data};
     CtxLease L;
     fv_r1cs_cross_term(*L.c, sp[0]->field, ip, ix, dt, sp[0]->rows, sp[0]->cols, z1, z2, e, u, flags, out);
+  });
+}
+
+// R1CSShape::is_sat_relaxed / is_sat (src/r1cs/mod.rs:474-574) as one call: the two commitments are begun first (start_commit, the
+// machinery behind nmx_commit_begin: each on its own context and stream), the equation pass (fieldvec.hip k_r1cs_sat) runs on this
+// call's stream while they accumulate, then both are collected and compared with the expected points on the host.  Every argument
+// check comes before anything is started; whatever fails later, ~PoolFuture has waited for the commitments that were begun.
+int nmx_r1cs_is_sat(uint64_t hA, uint64_t hB, uint64_t hC, uint64_t ck_handle, const void* W, size_t n_w, const void* E, size_t n_e,
+                    const void* u, const void* X, size_t n_io, const void* r_W, const void* r_E, const void* h_xy64,
+                    const void* comm_W_xy64, int comm_W_is_inf, const void* comm_E_xy64, int comm_E_is_inf, uint32_t flags,
+                    uint32_t* verdict, uint64_t* bad_rows, uint64_t* first_bad_row) {
+  return guarded([&] {
+    require(verdict != nullptr, NMX_E_ARG, "null argument");
+    ensure_init();  // no device: NMX_E_NO_DEVICE whatever the other arguments are (handles cannot exist without one)
+    require(!(flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_BASES_MONT)), NMX_E_ARG, "unsupported flag");
+    require((E == nullptr) == (u == nullptr), NMX_E_ARG, "E and u go together: both for is_sat_relaxed, neither for is_sat");
+    const bool relaxed = E != nullptr;
+    require((W || n_w == 0) && (X || n_io == 0), NMX_E_ARG, "null argument");
+    std::shared_ptr<Global::SparseSet> sp[3];
+    {
+      std::lock_guard<std::mutex> lk(G.mu);
+      const uint64_t hs[3] = {hA, hB, hC};
+      for (int j = 0; j < 3; j++) {
+        auto it = G.sparse.find(hs[j]);
+        if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
+        sp[j] = it->second;
+      }
+    }
+    for (int j = 0; j < 3; j++)
+      require(sp[j]->field == sp[0]->field && sp[j]->rows == sp[0]->rows && sp[j]->cols == sp[0]->cols, NMX_E_ARG,
+              "A, B, C must share field and shape");
+    const size_t rows = sp[0]->rows, cols = sp[0]->cols;
+    require(n_w <= cols && n_io <= cols && n_w + 1 + n_io == cols, NMX_E_ARG,
+            "W.len() + 1 + X.len() != number of columns (W.len() != num_vars or X.len() != num_io, src/r1cs/mod.rs:489-494)");
+    require(!relaxed || n_e == rows, NMX_E_ARG, "E.len() != num_cons (src/r1cs/mod.rs:489-494)");
+    require(rows < (1ull << 31), NMX_E_TOO_LARGE, "too many constraints");
+    BaseRef bs;
+    uint8_t exp_xy[2][64] = {};
+    bool exp_inf[2] = {true, true}, exp_valid[2] = {true, true};
+    const uint32_t cflags = flags & (NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_BASES_MONT);
+    if (ck_handle) {
+      bs = lookup(ck_handle);
+      const CurveOps& o = ops(bs->curve);
+      require(o.scalar_field == sp[0]->field, NMX_E_ARG, "the matrices are not over the scalar field of the key's curve");
+      require(n_w <= bs->n && (!relaxed || n_e <= bs->n), NMX_E_HANDLE, "ck shorter than W or E");
+      require(h_xy64 && r_W && (comm_W_xy64 || comm_W_is_inf), NMX_E_ARG, "null argument");
+      require(!relaxed || (r_E && (comm_E_xy64 || comm_E_is_inf)), NMX_E_ARG, "null argument");
+      const void* exp[2] = {comm_W_xy64, comm_E_xy64};
+      const int inf[2] = {comm_W_is_inf, comm_E_is_inf};
+      for (int j = 0; j < (relaxed ? 2 : 1); j++) {
+        exp_inf[j] = inf[j] != 0;
+        // an expected point that is not a point of the curve (or not canonical) equals no commitment: the bit is set, no error
+        if (!exp_inf[j]) exp_valid[j] = o.check_point_host((const uint8_t*)exp[j], flags, exp_xy[j]);
+      }
+    }
+    CtxLease L;
+    std::shared_ptr<PendingCommit> pc[2];
+    if (ck_handle) {
+      pc[0] = start_commit(bs, W, n_w, h_xy64, r_W, cflags);
+      if (relaxed) pc[1] = start_commit(bs, E, n_e, h_xy64, r_E, cflags);
+    }
+    const uint32_t* ip[3] = {sp[0]->indptr, sp[1]->indptr, sp[2]->indptr};
+    const uint32_t* ix[3] = {sp[0]->indices, sp[1]->indices, sp[2]->indices};
+    const uint32_t* dt[3] = {sp[0]->data, sp[1]->data, sp[2]->data};
+    uint64_t nbad = 0, first = ~0ull;
+    fv_r1cs_sat(*L.c, sp[0]->field, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags & (NMX_SCALARS_MONT | NMX_SCALARS_DEVICE), &nbad,
+                &first);
+    uint32_t v = nbad ? (uint32_t)NMX_UNSAT_EQ : 0u;
+    PendingCommit::Res res[2];
+    for (int j = 0; j < 2; j++)
+      if (pc[j]) res[j] = pc[j]->fut.get();  // (rethrows what the commitment threw; the other one is waited for by its destructor)
+    for (int j = 0; j < 2; j++) {
+      if (!pc[j]) continue;
+      const bool got_inf = res[j].inf != 0;
+      const bool same = exp_valid[j] && got_inf == exp_inf[j] && (got_inf || memcmp(res[j].out.data(), exp_xy[j], 64) == 0);
+      if (!same) v |= j == 0 ? (uint32_t)NMX_UNSAT_COMM_W : (uint32_t)NMX_UNSAT_COMM_E;
+    }
+    *verdict = v;
+    if (bad_rows) *bad_rows = nbad;
+    if (first_bad_row) *first_bad_row = first;
   });
 }
 

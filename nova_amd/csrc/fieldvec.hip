@@ -342,6 +342,48 @@ template <int FID> struct SpmvCrossFn {
     st<FID>(out, row, t);
   }
 };
+// R1CSShape::is_sat_relaxed / is_sat (src/r1cs/mod.rs:474-574), the equation half: does (A z)[row] (B z)[row] == u (C z)[row] + E[row]
+// hold on every row (RELAXED), or (A z)(B z) == C z (strict: no E, u = 1 -- no load of e, no product by u)?  The residual of
+// SpmvCrossFn, DECIDED here instead of stored: nothing rows-sized is written.  A wave reduces its 64 predicates with one ballot; only a
+// wave that saw a violation touches memory -- one atomicAdd on the violation count and one atomicMin on the lowest violating row, both
+// issued by its lowest violating lane -- so a satisfied instance issues no atomics and no stores at all.  No early exit: the
+// count is exact and the run time does not depend on the data.
+//
+// The comparison is on the CANONICAL residue.  norm() only propagates carries: what it leaves is some representative of the
+// residue, and a zero residual arrives here as p, 2p or 3p, never as literal zero.  Bounds on the value handed to canon() (which
+// is valid for normalized values below 16 p and returns the representative in [0, p)):
+//   az, bz, cz, e canonical (< p; e is reduced on load -- E is caller data -- which also keeps it under sub2's 2p - 2^233);
+//   ab = az * bz < 1.01 p;  u, k canonical constants
+//   RELAXED:  t = mul_add(ab, k, cz, u) < p (1 + (1.01 + 1) / 127) < 1.02 p;   t - e + 2p  in (p, 3.02 p)
+//   strict:   t = ab * k < 1.01 p;                                             t - cz + 2p in (p, 3.01 p)
+// so canon() applies, and the residual is zero mod p exactly when all nine limbs of its output are zero.
+struct R1csSatArgs {
+  const uint32_t *ipA, *ixA, *dA, *ipB, *ixB, *dB, *ipC, *ixC, *dC;
+  const uint32_t *z, *e;
+  unsigned long long* rec;  // [0] number of violated rows, [1] lowest violated row (reset to 0 / 2^64 - 1 on the stream before the launch)
+  uint32_t rows, colmask;
+};
+template <int FID, bool RELAXED> __global__ __launch_bounds__(256) void k_r1cs_sat(R1csSatArgs a, Fp<FID> u, Fp<FID> k) {
+  using F = Fp<FID>;
+  const uint32_t row = blockIdx.x * 256u + threadIdx.x;
+  bool bad = false;
+  if (row < a.rows) {
+    const F az = spmv_row<FID>(a.ipA, a.ixA, a.dA, a.z, a.colmask, row).canon();
+    const F bz = spmv_row<FID>(a.ipB, a.ixB, a.dB, a.z, a.colmask, row).canon();
+    const F cz = spmv_row<FID>(a.ipC, a.ixC, a.dC, a.z, a.colmask, row).canon();
+    const F ab = az * bz;
+    F t;
+    if constexpr (RELAXED) t = F::sub2(F::mul_add(ab, k, cz, u), ld<FID>(a.e, row).canon()).norm();
+    else t = F::sub2(ab * k, cz).norm();
+    bad = !t.canon().is_zero_limbs();
+  }
+  const unsigned long long m = __ballot(bad);  // rows of a wave are consecutive: its lowest violating lane holds its lowest violating row
+  if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll(m) - 1)) {
+    atomicAdd(a.rec, (unsigned long long)__popcll(m));
+    atomicMin(a.rec + 1, (unsigned long long)row);
+  }
+}
+
 // NIFS fold in one launch (src/r1cs/mod.rs:1058-1067): W = W1 + r W2 over n_w elements, E = E1 + r T over n_e
 template <int FID> struct FoldPairFn {
   const uint32_t *w1, *w2, *e1, *t;
@@ -1262,6 +1304,76 @@ static void r1cs_cross_term_t(Ctx& c, const uint32_t* const* ip, const uint32_t*
                      cols <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu, nu, k};
   timed_launch(c, f, rows, &io);
 }
+// The equation half of is_sat / is_sat_relaxed (k_r1cs_sat).  z = [W, u, X] is assembled in the context arena (strict: u = 1 in the
+// vectors' form), W (and E) from HBM or from the host as `flags` says, u and X always from the host.  The 16-byte result record
+// is reset on the stream before the launch and comes back through the context's pinned buffer.  E == nullptr: strict.
+template <int FID>
+static void r1cs_sat_t(Ctx& c, const uint32_t* const* ip, const uint32_t* const* ix, const uint32_t* const* dt, size_t rows, size_t cols,
+                       const void* W, size_t n_w, const void* E, const void* u, const void* X, size_t n_io, uint32_t flags, uint64_t* bad_rows,
+                       uint64_t* first_bad_row) {
+  using F = Fp<FID>;
+  const bool mont = flags & NMX_SCALARS_MONT, dev = flags & NMX_SCALARS_DEVICE, relaxed = E != nullptr;
+  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
+  // u as the kernel takes it, (p - u) * 2^261 (CrossTermFn), and as z holds it: the caller's word, or ONE in the vectors' form
+  uint32_t uw[8] = {1, 0, 0, 0, 0, 0, 0, 0};
+  F nu = F::zero();
+  if (relaxed) {
+    nu = F::sub2(F::zero(), challenge<FID>(u, mont)).norm().canon();  // (NMX_E_SCALAR_RANGE for u >= p, before anything is enqueued)
+    memcpy(uw, u, 32);
+  } else if (mont) {  // 2^256 mod p as a plain integer = the internal form of 1/32 (eq_evals_t)
+    F two5 = F::zero();
+    two5.l[0] = 32;
+    two5.to_internal().canon().inv().canon().to_words(uw);
+  }
+  const F k = mont ? F::from_limbs(FpParams<FID>::C266) : F::from_limbs(FpParams<FID>::R2);
+  const bool stage_e = relaxed && !dev;
+  arena_reserve(c, 256 + pad(cols * 32) + (stage_e ? pad(rows * 32) : 0) + 256);
+  if (!c.pinned) HIPCHK(hipHostMalloc((void**)&c.pinned, DeviceBackend::kPinnedBytes, hipHostMallocDefault));
+  unsigned long long* rec = (unsigned long long*)c.arena;
+  char* dz = c.arena + 256;
+  const uint32_t* de = (const uint32_t*)E;
+  // pinned: [0, 16) the record's landing zone, [64, 80) its reset value, [128, 160) u
+  unsigned long long* land = (unsigned long long*)c.pinned;
+  unsigned long long* init = (unsigned long long*)(c.pinned + 64);
+  land[0] = 0, land[1] = ~0ull;
+  init[0] = 0, init[1] = ~0ull;
+  memcpy(c.pinned + 128, uw, 32);
+  const bool prof = G.profiling;
+  DeviceBackend be(c, false, prof);
+  try {
+    HIPCHK(hipMemcpyAsync(rec, init, 16, hipMemcpyHostToDevice, c.stream));
+    if (n_w) HIPCHK(hipMemcpyAsync(dz, W, n_w * 32, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, c.stream));
+    HIPCHK(hipMemcpyAsync(dz + n_w * 32, c.pinned + 128, 32, hipMemcpyHostToDevice, c.stream));
+    if (n_io) HIPCHK(hipMemcpyAsync(dz + (n_w + 1) * 32, X, n_io * 32, hipMemcpyHostToDevice, c.stream));
+    if (stage_e) {
+      char* d = dz + pad(cols * 32);
+      HIPCHK(hipMemcpyAsync(d, E, rows * 32, hipMemcpyHostToDevice, c.stream));
+      de = (const uint32_t*)d;
+    }
+    be.mark("kernel");
+    if (rows) {
+      const R1csSatArgs a{ip[0], ix[0], dt[0], ip[1], ix[1], dt[1], ip[2], ix[2], dt[2], (const uint32_t*)dz, de, rec, (uint32_t)rows,
+                          cols <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu};
+      const dim3 grid((uint32_t)((rows + 255) / 256)), block(256);  // one row per lane, as k_launch<SpmvCrossFn>: the same latency-bound gather
+      if (relaxed) hipLaunchKernelGGL((k_r1cs_sat<FID, true>), grid, block, 0, c.stream, a, nu, k);
+      else hipLaunchKernelGGL((k_r1cs_sat<FID, false>), grid, block, 0, c.stream, a, nu, k);
+      HIPCHK(hipGetLastError());
+    }
+    be.mark("end");
+    HIPCHK(hipMemcpyAsync(land, rec, 16, hipMemcpyDeviceToHost, c.stream));
+    stream_wait(c.stream);
+  } catch (...) {
+    (void)hipStreamSynchronize(c.stream);  // nothing of this call still reads the caller's vectors
+    throw;
+  }
+  *bad_rows = land[0];
+  *first_bad_row = land[1];
+  if (prof && be.nmarks == 2) {
+    float ms = 0;
+    HIPCHK(hipEventElapsedTime(&ms, c.ev[0], c.ev[1]));
+    prof_store(&ms, 1);
+  }
+}
 template <int FID>
 static void nifs_fold_t(Ctx& c, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e, const void* r,
                         uint32_t flags, void* w, void* e) {
@@ -1784,6 +1896,17 @@ void fv_r1cs_cross_term(Ctx& c, int field, const uint32_t* const* ip, const uint
     case 1: r1cs_cross_term_t<1>(c, ip, ix, dt, rows, cols, z1, z2, e, u, flags, out); break;
     case 2: r1cs_cross_term_t<2>(c, ip, ix, dt, rows, cols, z1, z2, e, u, flags, out); break;
     case 3: r1cs_cross_term_t<3>(c, ip, ix, dt, rows, cols, z1, z2, e, u, flags, out); break;
+    default: throw Fail{NMX_E_ARG, "bad field id"};
+  }
+}
+void fv_r1cs_sat(Ctx& c, int field, const uint32_t* const* ip, const uint32_t* const* ix, const uint32_t* const* dt, size_t rows, size_t cols,
+                 const void* W, size_t n_w, const void* E, const void* u, const void* X, size_t n_io, uint32_t flags, uint64_t* bad_rows,
+                 uint64_t* first_bad_row) {
+  switch (field) {
+    case 0: r1cs_sat_t<0>(c, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); break;
+    case 1: r1cs_sat_t<1>(c, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); break;
+    case 2: r1cs_sat_t<2>(c, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); break;
+    case 3: r1cs_sat_t<3>(c, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); break;
     default: throw Fail{NMX_E_ARG, "bad field id"};
   }
 }

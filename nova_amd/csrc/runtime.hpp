@@ -715,6 +715,11 @@ void fv_bind(Ctx&, int field, const void* z, size_t z_len, size_t lo_off, size_t
 void fv_suffix_horner(Ctx&, int field, const void* f, size_t n, const void* u, uint32_t flags, void* out);
 void fv_r1cs_cross_term(Ctx&, int field, const uint32_t* const* indptr, const uint32_t* const* indices, const uint32_t* const* data,
                         size_t rows, size_t cols, const void* z1, const void* z2, const void* e, const void* u, uint32_t flags, void* out);
+// is_sat / is_sat_relaxed, the equation half (fieldvec.hip k_r1cs_sat): z = [W, u, X]; E == nullptr: strict (u ignored).  W, E follow
+// NMX_SCALARS_DEVICE, u and X are host pointers.  Synchronous: *bad_rows = violated rows, *first_bad_row = the lowest (2^64 - 1: none)
+void fv_r1cs_sat(Ctx&, int field, const uint32_t* const* indptr, const uint32_t* const* indices, const uint32_t* const* data, size_t rows,
+                 size_t cols, const void* W, size_t n_w, const void* E, const void* u, const void* X, size_t n_io, uint32_t flags,
+                 uint64_t* bad_rows, uint64_t* first_bad_row);
 void fv_nifs_fold(Ctx&, int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e, const void* r,
                   uint32_t flags, void* w, void* e);
 void fv_eq_evals(Ctx&, int field, const void* r_host, uint32_t ell, uint32_t flags, uint32_t* d_out);

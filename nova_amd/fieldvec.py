@@ -490,3 +490,78 @@ def sumcheck_prove_batch_eval(field, claims, num_rounds, polys, eq_points, coeff
     _check(L.lib().nmx_sumcheck_prove_batch_eval(field, cl.ctypes.data, nrs, pp, qp, co.ctypes.data, k, _flags(dev, mont), cb, ctx,
                                                 out_p.ctypes.data, r.ctypes.data, fin.ctypes.data))
     return _rows(out_p, nmax, 3), [x[0] for x in _rows(r, nmax, 1)], [x[0] for x in _rows(fin, k, 1)]
+
+
+# ---- R1CSShape::is_sat / is_sat_relaxed as one call (nmx_r1cs_is_sat; src/r1cs/mod.rs:474-574) -----------------------------------
+class SatResult:
+    """Answer of r1cs_is_sat / r1cs_is_sat_relaxed.  `ok` is the reference's Ok(()); eq_ok false is its UnSat "... is unsatisfiable",
+    eq_ok true with a comm_*_ok false its UnSat "Invalid commitment(s)" (the reference reports the equation first).  bad_rows = number of
+    violated constraints, first_bad_row = the lowest one (None when there is none)."""
+
+    def __init__(self, verdict, bad_rows, first_bad_row):
+        self.verdict = verdict
+        self.eq_ok = not (verdict & L.UNSAT_EQ)
+        self.comm_W_ok = not (verdict & L.UNSAT_COMM_W)
+        self.comm_E_ok = not (verdict & L.UNSAT_COMM_E)
+        self.ok = verdict == 0
+        self.bad_rows = bad_rows
+        self.first_bad_row = None if first_bad_row == 2 ** 64 - 1 else first_bad_row
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return (f"SatResult(ok={self.ok}, eq_ok={self.eq_ok}, comm_W_ok={self.comm_W_ok}, comm_E_ok={self.comm_E_ok}, "
+                f"bad_rows={self.bad_rows}, first_bad_row={self.first_bad_row})")
+
+
+def _expected_point(c):
+    """Commitment / (xy64, is_inf) / 64 bytes (all zero = the identity) -> (array, is_inf)"""
+    if c is None:
+        return None, 0
+    if hasattr(c, "xy"):
+        xy, inf = c.xy, c.is_inf
+    elif isinstance(c, (tuple, list)) and len(c) == 2:
+        xy, inf = c
+    else:
+        xy, inf = c, None
+    a = _host_u8(xy, 64)
+    assert a.size == 64
+    return a, int(bool(inf) if inf is not None else not a.any())
+
+
+def _is_sat(A, B, C, ck, W, E, u, X, comm_W, comm_E, r_W, r_E, h, mont):
+    import ctypes
+    pw, nw, dev, _kw = _vec(W)
+    pe, ne = None, 0
+    if E is not None:
+        pe, ne, deve, _ke = _vec(E)
+        assert deve == dev, "W and E: both in HBM or both on the host"
+    xx = _host_u8(X, 32)
+    uu = _chal(u) if u is not None else None
+    rw = _host_u8(bytes(32) if r_W is None else r_W, 32)
+    re_ = _host_u8(bytes(32) if r_E is None else r_E, 32)
+    cw, cw_inf = _expected_point(comm_W)
+    ce, ce_inf = _expected_point(comm_E)
+    hh = _host_u8((ck.h if ck is not None else bytes(64)) if h is None else h, 64)
+    flags = _flags(dev, mont) | (L.BASES_MONT if (ck is not None and ck.mont) else 0)
+    verdict, bad, first = ctypes.c_uint32(0), ctypes.c_uint64(0), ctypes.c_uint64(0)
+    ptr = lambda a: None if a is None else a.ctypes.data
+    _check(L.lib().nmx_r1cs_is_sat(A.handle, B.handle, C.handle, ck.handle if ck is not None else 0, pw, nw, pe, ne, ptr(uu),
+                                   xx.ctypes.data if xx.size else None, xx.size // 32, rw.ctypes.data, re_.ctypes.data, hh.ctypes.data,
+                                   ptr(cw), cw_inf, ptr(ce), ce_inf, flags, ctypes.byref(verdict), ctypes.byref(bad), ctypes.byref(first)))
+    return SatResult(verdict.value, bad.value, first.value)
+
+
+def r1cs_is_sat(A, B, C, ck, W, X, comm_W, r_W=None, h=None, mont=False):
+    """R1CSShape::is_sat (src/r1cs/mod.rs:532-574): (A z)(B z) == C z on every row with z = [W, 1, X], and commit(ck, W, r_W) == comm_W.
+    A, B, C: SparseMatrix of one shape over the scalar field of ck's curve; W: CUDA tensor (used in place) or host array (uploaded);
+    X: host; comm_W: Commitment, (xy64, is_inf) or 64 bytes, in the key's form (Montgomery when ck.mont, like h); ck=None: the equation
+    only.  Returns a SatResult."""
+    return _is_sat(A, B, C, ck, W, None, None, X, comm_W, None, r_W, None, h, mont)
+
+
+def r1cs_is_sat_relaxed(A, B, C, ck, W, E, u, X, comm_W, comm_E, r_W=None, r_E=None, h=None, mont=False):
+    """R1CSShape::is_sat_relaxed (src/r1cs/mod.rs:474-529): (A z)(B z) == u (C z) + E with z = [W, u, X], commit(ck, W, r_W) == comm_W
+    and commit(ck, E, r_E) == comm_E -- the two commitments run beside the equation pass.  Operands as r1cs_is_sat."""
+    return _is_sat(A, B, C, ck, W, E, u, X, comm_W, comm_E, r_W, r_E, h, mont)
