@@ -63,6 +63,7 @@ enum {
                                    read by the host before one of the two.  The NIFS chain between two commitments --
                                    Z = W1 + W2, AZ / BZ / CZ, T (src/r1cs/mod.rs:590-622), the folds (1044-1107) -- is the
                                    intended use: five dependent launches with no host wake-up between them.          */
+  NMX_IPA_B_IS_POINT = 1u << 10, /* nmx_ipa_verify: `b` is the evaluation point (log2(n) elements, host) instead of U.b_vec */
   NMX_OUT_PARTIAL = 1u << 4     /* write a 128-byte partial sum instead of an affine point: the per-GPU   */
                                 /* result of a sharded MSM, input of nmx_point_sum.  Format: extended     */
                                 /* Jacobian (X, Y, ZZ, ZZZ), x = X/ZZ, y = Y/ZZZ, each coordinate the     */
@@ -479,6 +480,38 @@ typedef int (*nmx_ipa_transcript_fn)(void* ctx, const uint8_t* L_xy64, int L_is_
                                      uint8_t* r32_out);
 int nmx_ipa_prove(uint64_t ck_handle, const void* ck_c_xy64, const void* a, const void* b, size_t n, uint32_t flags,
                   nmx_ipa_transcript_fn transcript, void* ctx, uint8_t* out_L, uint8_t* out_R, uint8_t* out_is_inf, uint8_t* out_a_hat);
+/* InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390), reached through EvaluationEngine::verify (:80-99) from
+ * RelaxedR1CSSNARK::verify (src/spartan/snark.rs:384, ppsnark.rs:1645) inside CompressedSNARK::verify (src/nova/mod.rs:912), from the
+ * point where the caller's transcript has produced its challenges: the verifier's transcript never waits for the device (it absorbs
+ * L_vec[i], R_vec[i] from the proof and squeezes, :315-321), so there is no callback.  The work linear in n -- the tensor vector
+ * s[i] = prod_k (bit_{ell-1-k}(i) ? r_k : r_k^-1) (:335-349), ck_hat = commit(ck, s) (:351-354) and <b_vec, s> (:356) -- runs on the
+ * device: s is generated in HBM next to the registered key (one product per element, nova_amd/csrc/ipa_verify.hpp) and never crosses
+ * the bus; the O(log n) group side (:358-376) runs on host threads under the MSM.
+ *   ck_handle   the Pedersen key, registered; its first n points are used (`ck.split_at(U.b_vec.len())`, :294); n beyond it:
+ *               NMX_E_HANDLE.  Keys over several devices work as for nmx_commit.
+ *   ck_c_xy64   host, 64 bytes: the ALREADY SCALED one-point key `ck_c.scale(&r)` (:309-310), as nmx_ipa_prove takes it
+ *   comm_a_xy64, comm_a_is_inf, c   U.comm_a_vec (may be null when it is the identity) and U.c (32 bytes) (:312-313)
+ *   b, n        U.b_vec: n elements, n a power of two below 2^31 (:297-303); host, or HBM with NMX_SCALARS_DEVICE.  With
+ *               NMX_IPA_B_IS_POINT: the evaluation point instead, log2(n) elements on the host, point[0] the most significant
+ *               variable as in nmx_eq_evals_from_points -- the eq table EvaluationEngine::verify builds (:88) is never materialised:
+ *               <eq(point), s> = prod_k ((1 - point_k) r_k^-1 + point_k r_k).  Not modified.
+ *   L_xy64, R_xy64   log2(n) points of 64 bytes each (L_vec, R_vec); is_inf (may be null = none): 2 log2(n) bytes in nmx_ipa_prove's
+ *               out_is_inf layout; a_hat: 32 bytes.  A proof goes from nmx_ipa_prove into this call unchanged.
+ *   rs          log2(n) challenges, host, round 0 first (:315-321).  rs[k] >= modulus: NMX_E_SCALAR_RANGE; rs[k] = 0: NMX_E_ZERO
+ *               (`batch_invert(&r)?` fails, :328)
+ *   verdict     0 = the proof is accepted, NMX_IPA_REJECT = P_hat != commit(ck_hat || ck_c, a_hat || a_hat b_hat) (NovaError::InvalidPCS,
+ *               :378-388).  The result is NMX_OK whenever the check RAN.
+ *   out_ck_hat_xy64, out_ck_hat_is_inf, out_b_hat   (each may be null) the two intermediate values, commit(ck, s, 0) (canonical x || y
+ *               like every result) and <b_vec, s> (in the scalars' form): they make a rejection diagnosable.
+ * Flags: NMX_SCALARS_MONT (c, b / point, a_hat, rs, out_b_hat are Montgomery limbs), NMX_SCALARS_DEVICE (b only; NMX_E_ARG together
+ * with NMX_IPA_B_IS_POINT), NMX_BASES_MONT (ck_c, comm_a, L, R are), NMX_IPA_B_IS_POINT; anything else NMX_E_ARG.  Null arguments and
+ * the length rules are NMX_E_ARG before a device or a key is touched; a point of the proof or comm_a that is not canonical or not on
+ * the curve: NMX_E_POINT (the reference cannot deserialise it).  On an error nothing is written.  n = 1: no round, s = [1], the
+ * equation is still checked.  Synchronous, ordered behind the calling thread's NMX_ASYNC calls; thread-safe like nmx_ipa_prove. */
+enum { NMX_IPA_REJECT = 1u << 0 };
+int nmx_ipa_verify(uint64_t ck_handle, const void* ck_c_xy64, const void* comm_a_xy64, int comm_a_is_inf, const void* c, const void* b,
+                   size_t n, const void* L_xy64, const void* R_xy64, const uint8_t* is_inf, const void* a_hat, const void* rs,
+                   uint32_t flags, uint32_t* verdict, uint8_t* out_ck_hat_xy64, uint8_t* out_ck_hat_is_inf, uint8_t* out_b_hat);
 /* PolyEvalWitness::batch / batch_diff_size (src/spartan/mod.rs:165-277): out[i] = sum_j s^j * vecs[j][i], i < n_out,
  * vectors shorter than n_out read as zero-padded; every lens[j] <= n_out.  `vecs`, `lens`, `s` are host arrays; the
  * vectors themselves and `out` follow NMX_SCALARS_DEVICE. */

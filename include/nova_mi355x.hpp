@@ -365,6 +365,35 @@ InnerProductArgument prove(const CommitmentKey& ck, const Affine& ck_c, const st
   }
   return out;
 }
+// InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) from the point where the caller's transcript has produced `rs` (it absorbs
+// L_vec[i], R_vec[i] and squeezes, :315-321; round 0 first).  `b`: U.b_vec (n elements), or with b_is_point the evaluation point of
+// EvaluationEngine::verify (:80-99; log2(n) elements, the eq table is never built).  true: accepted; false: NovaError::InvalidPCS.
+namespace detail {
+inline bool verify_call(const CommitmentKey& ck, const Affine& ck_c, const Point& comm_a, const Scalar& c, const void* b, size_t n,
+                        const InnerProductArgument& proof, const std::vector<Scalar>& rs, uint32_t flags) {
+  const size_t rounds = proof.L_vec.size();
+  if (proof.R_vec.size() != rounds || rs.size() != rounds || n != ((size_t)1 << rounds))
+    throw std::invalid_argument("InvalidInputLength (ipa_pc.rs:297-303)");
+  std::vector<uint8_t> L(64 * rounds + 1), R(64 * rounds + 1), inf(2 * rounds + 1);
+  for (size_t k = 0; k < rounds; k++) {
+    std::copy(proof.L_vec[k].xy.begin(), proof.L_vec[k].xy.end(), L.begin() + 64 * k);
+    std::copy(proof.R_vec[k].xy.begin(), proof.R_vec[k].xy.end(), R.begin() + 64 * k);
+    inf[2 * k] = proof.L_vec[k].is_inf, inf[2 * k + 1] = proof.R_vec[k].is_inf;
+  }
+  uint32_t verdict = 0;
+  check(nmx_ipa_verify(ck.handle(), ck_c.data(), comm_a.xy.data(), comm_a.is_inf ? 1 : 0, c.data(), b, n, L.data(), R.data(), inf.data(),
+                       proof.a_hat.data(), rs.data(), flags | (ck.mont() ? NMX_BASES_MONT : 0u), &verdict, nullptr, nullptr, nullptr));
+  return verdict == 0;
+}
+}  // namespace detail
+inline bool verify(const CommitmentKey& ck, const Affine& ck_c, const Point& comm_a, const Scalar& c, const std::vector<Scalar>& b,
+                   const InnerProductArgument& proof, const std::vector<Scalar>& rs, bool mont = false, bool b_is_point = false) {
+  const size_t n = b_is_point ? (size_t)1 << b.size() : b.size();
+  if (b.empty() && !b_is_point) throw std::invalid_argument("InvalidInputLength (ipa_pc.rs:297-303)");
+  const Scalar none{};
+  return detail::verify_call(ck, ck_c, comm_a, c, b.empty() ? none.data() : b.data()->data(), n, proof, rs,
+                             (mont ? NMX_SCALARS_MONT : 0u) | (b_is_point ? NMX_IPA_B_IS_POINT : 0u));
+}
 }  // namespace ipa
 
 // Hosts that keep their vectors in HBM between provider calls (INTEGRATION.md sections 2b-2e: the patched r1cs/mod.rs, nifs.rs,
@@ -536,6 +565,11 @@ inline IpaProof ipa_prove(const CommitmentKey& ck, const Affine& ck_c, const voi
   check(nmx_ipa_prove(ck.handle(), ck_c.data(), a, b, n, kDev, cb, ctx, p.L.data(), p.R.data(), p.inf.data(), p.a_hat.data()));
   p.L.resize(64 * rounds), p.R.resize(64 * rounds), p.inf.resize(2 * rounds);
   return p;
+}
+// InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) over an HBM-resident b_vec of n elements
+inline bool ipa_verify(const CommitmentKey& ck, const Affine& ck_c, const provider::Point& comm_a, const Scalar& c, const void* b, size_t n,
+                       const ipa::InnerProductArgument& proof, const std::vector<Scalar>& rs, bool mont = false) {
+  return ipa::detail::verify_call(ck, ck_c, comm_a, c, b, n, proof, rs, kDev | (mont ? NMX_SCALARS_MONT : 0u));
 }
 }  // namespace resident
 }  // namespace nova

@@ -10,6 +10,7 @@ SCALARS_MONT, BASES_MONT, SCALARS_DEVICE, BASES_DEVICE, OUT_PARTIAL, BASES_PRECO
 BASES_NOCACHE = 128
 SCALARS_SHARDED = 256
 ASYNC = 512
+IPA_B_IS_POINT = 1024  # nmx_ipa_verify: b is the evaluation point
 OP_AXPY, OP_AXPY2, OP_CROSS_TERM, OP_CROSS_TERM2, OP_VEC_ADD = range(5)
 BRANCH_NAMES = {0: "host", 1: "local", 2: "peer_copy", 3: "shard_resident", 4: "none"}
 PROF_STAGES = 12
@@ -23,6 +24,7 @@ E_ARG, E_NO_DEVICE, E_HIP, E_SCALAR_RANGE, E_SMALL_RANGE, E_HANDLE, E_TOO_LARGE 
 E_IO, E_FORMAT, E_POINT, E_ZERO = -8, -9, -10, -11
 BITS_AUTO = 0xFFFFFFFF
 UNSAT_EQ, UNSAT_COMM_W, UNSAT_COMM_E = 1, 2, 4  # nmx_r1cs_is_sat's verdict bits
+IPA_REJECT = 1  # nmx_ipa_verify's verdict bit
 
 # nmx_transcript_fn: (ctx, round polynomial coefficients, how many, challenge out) -> 0
 TRANSCRIPT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t,
@@ -123,6 +125,7 @@ def lib():
     L.nmx_sumcheck_prove_quad_prod.argtypes = [i, vp, sz, vp, vp, u32, TRANSCRIPT_FN, vp, vp, vp, vp]
     L.nmx_sumcheck_prove_batch_eval.argtypes = [i, vp, vp, vp, vp, vp, sz, u32, TRANSCRIPT_FN, vp, vp, vp, vp]
     L.nmx_ipa_prove.argtypes = [u64, vp, vp, vp, sz, u32, IPA_TRANSCRIPT_FN, vp, vp, vp, vp, vp]
+    L.nmx_ipa_verify.argtypes = [u64, vp, vp, i, vp, vp, sz, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.nmx_set_profiling.argtypes = [i]
     L.nmx_profile_last.argtypes = [ctypes.POINTER(ctypes.c_float), i]
     L.nmx_set_window_bits.argtypes = [u32]

@@ -2830,6 +2830,143 @@ int nmx_ipa_prove(uint64_t ck_handle, const void* ck_c_xy64, const void* a, cons
   });
 }
 
+// InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) as one call.  Every argument check comes first; then the challenges
+// are validated and turned into r^2, r^-2 and the kernel's constants on the host (ipa_verify.hpp), the O(log n) left side
+//   P_hat = sum r_k^2 L_k + sum r_k^-2 R_k + comm_a + c ck_c                                                   (:358-376)
+// is begun on pool threads (host scalar multiplications, each job sums its share into one partial), and under them this thread
+// launches k_ipa_s (s into HBM, the block partials of <b, s>) and the MSM of s over the registered key -- ck_hat (:351-354).
+// The right side a_hat ck_hat + (a_hat b_hat) ck_c (:378-388) and the comparison of the two affine points are host work.
+int nmx_ipa_verify(uint64_t ck_handle, const void* ck_c_xy64, const void* comm_a_xy64, int comm_a_is_inf, const void* c_sc, const void* b,
+                   size_t n, const void* L_xy64, const void* R_xy64, const uint8_t* is_inf, const void* a_hat, const void* rs,
+                   uint32_t flags, uint32_t* verdict, uint8_t* out_ck_hat_xy64, uint8_t* out_ck_hat_is_inf, uint8_t* out_b_hat) {
+  return guarded([&] {
+    require(verdict && ck_c_xy64 && c_sc && b && a_hat && (comm_a_xy64 || comm_a_is_inf), NMX_E_ARG, "null argument");
+    require(!(flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_BASES_MONT | NMX_IPA_B_IS_POINT)), NMX_E_ARG, "unsupported flag");
+    const bool point = (flags & NMX_IPA_B_IS_POINT) != 0, dev = (flags & NMX_SCALARS_DEVICE) != 0;
+    require(!(point && dev), NMX_E_ARG, "the evaluation point is a host array");
+    // n != 1 << L_vec.len(), L_vec.len() != R_vec.len(), L_vec.len() >= 32 (:297-303)
+    require(n >= 1 && (n & (n - 1)) == 0 && n < ((size_t)1 << 31), NMX_E_ARG, "n must be a power of two below 2^31");
+    uint32_t ell = 0;
+    while (((size_t)1 << ell) < n) ell++;
+    require(ell == 0 || (L_xy64 && R_xy64 && rs), NMX_E_ARG, "null argument");
+    ensure_init();
+    auto bs = lookup(ck_handle);
+    require(n <= bs->n, NMX_E_HANDLE, "ck shorter than the vectors");  // ck.split_at(U.b_vec.len()) would panic (:294)
+    const CurveOps& o = ops(bs->curve);
+    const int field = o.scalar_field;
+    const uint32_t sflags = flags & NMX_SCALARS_MONT, pflags = flags & (NMX_SCALARS_MONT | NMX_BASES_MONT);
+    // the terms of P_hat: (point in the caller's form, scalar in the scalars' form); identity points contribute nothing
+    struct Term {
+      uint8_t xy[64], sc[32];
+      uint32_t fl;
+    };
+    auto terms = std::make_shared<std::vector<Term>>();
+    uint8_t canon_xy[64];
+    auto add_term = [&](const void* xy, bool inf, const void* sc, uint32_t fl) {
+      if (inf) return;
+      require(o.check_point_host((const uint8_t*)xy, flags, canon_xy), NMX_E_POINT, "a point of the proof is not canonical or not on the curve");
+      Term t;
+      memcpy(t.xy, xy, 64);
+      if (sc) memcpy(t.sc, sc, 32);
+      t.fl = fl;
+      terms->push_back(t);
+    };
+    uint8_t one[32] = {1};
+    add_term(ck_c_xy64, false, c_sc, pflags);                                              // c * ck_c
+    add_term(comm_a_xy64, comm_a_is_inf != 0, one, pflags & ~(uint32_t)NMX_SCALARS_MONT);  // comm_a
+    const size_t fixed_terms = terms->size();
+    for (uint32_t k = 0; k < ell; k++) {
+      add_term((const uint8_t*)L_xy64 + 64 * k, is_inf && is_inf[2 * k], nullptr, pflags);
+      add_term((const uint8_t*)R_xy64 + 64 * k, is_inf && is_inf[2 * k + 1], nullptr, pflags);
+    }
+    uint8_t ab[32];
+    fv_field_mul_host(field, a_hat, c_sc, sflags, ab);  // (the range check of a_hat and c, before anything is started)
+    CtxLease L;
+    Ctx& c = *L.c;
+    auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
+    const size_t full = pad(n * 32), total = full + ((point || dev) ? 0 : full);
+    struct Own {
+      void* p = nullptr;
+      ~Own() {
+        if (p) (void)hipFree(p);
+      }
+    } own;
+    char* base;
+    if (total <= ((size_t)64 << 20)) {
+      aux_reserve(c, total);
+      base = c.aux;
+    } else {
+      HIPCHK(hipMalloc(&own.p, total));
+      base = (char*)own.p;
+    }
+    uint32_t* s_dev = (uint32_t*)base;
+    const uint32_t* b_dev = nullptr;
+    std::vector<uint8_t> rsq(32 * (size_t)ell + 32), rinvsq(32 * (size_t)ell + 32);
+    uint8_t b_hat[32], ck_hat[64] = {}, ck_hat_inf = 0;
+    try {
+      if (!point) {
+        if (dev) {
+          b_dev = (const uint32_t*)b;
+        } else {
+          HIPCHK(hipMemcpyAsync(base + full, b, n * 32, hipMemcpyHostToDevice, c.stream));
+          b_dev = (const uint32_t*)(base + full);
+        }
+      }
+      const uint32_t* partial_host = nullptr;
+      uint32_t blocks = 0;
+      fv_ipa_verify_s(c, field, rs, ell, point ? b : nullptr, sflags, 0, n, s_dev, b_dev, rsq.data(), rinvsq.data(), b_hat, &partial_host, &blocks);
+      // the left side on pool threads, under the device work.  L_k takes r_k^2, R_k takes r_k^-2 (identities were skipped above)
+      {
+        size_t at = fixed_terms;
+        for (uint32_t k = 0; k < ell; k++) {
+          if (!(is_inf && is_inf[2 * k])) memcpy((*terms)[at++].sc, rsq.data() + 32 * (size_t)k, 32);
+          if (!(is_inf && is_inf[2 * k + 1])) memcpy((*terms)[at++].sc, rinvsq.data() + 32 * (size_t)k, 32);
+        }
+      }
+      const size_t jobs = std::min<size_t>(terms->size(), 12);
+      std::vector<PoolFuture<std::array<uint8_t, 128>>> lhs;
+      lhs.reserve(jobs);
+      for (size_t j = 0; j < jobs; j++)
+        lhs.emplace_back([terms, j, jobs, &o] {
+          std::vector<uint8_t> parts;
+          for (size_t i = j; i < terms->size(); i += jobs) {
+            parts.resize(parts.size() + 128);
+            o.blind_term((*terms)[i].xy, (*terms)[i].sc, (*terms)[i].fl, parts.data() + parts.size() - 128);
+          }
+          std::array<uint8_t, 128> sum;
+          o.point_sum(parts.data(), parts.size() / 128, NMX_OUT_PARTIAL, sum.data(), nullptr);
+          return sum;
+        });
+      if (!bs->parts.empty()) stream_wait(c.stream);  // the shards' streams read s from this device
+      stat_add(NMX_STAT_MSM_CALLS);
+      key_msm(c, *bs, 0, n, field_call(s_dev, NMX_SCALARS_DEVICE), NMX_SCALARS_DEVICE, ck_hat, &ck_hat_inf);
+      stream_wait(c.stream);
+      if (!point) fv_ipa_verify_bhat(field, partial_host, blocks, sflags, b_hat);
+      fv_field_mul_host(field, a_hat, b_hat, sflags, ab);
+      // right side: a_hat * ck_hat + (a_hat * b_hat) * ck_c (:378-388)
+      uint8_t rhs[256], rhs_xy[64], lhs_xy[64], rhs_inf = 0, lhs_inf = 0;
+      size_t nr = 0;
+      if (!ck_hat_inf) o.blind_term(ck_hat, a_hat, sflags, rhs + 128 * nr++);  // (ck_hat is canonical whatever the key's form)
+      o.blind_term(ck_c_xy64, ab, pflags, rhs + 128 * nr++);
+      o.point_sum(rhs, nr, 0, rhs_xy, &rhs_inf);
+      std::vector<uint8_t> lp(128 * jobs);
+      for (size_t j = 0; j < jobs; j++) {
+        const auto t = lhs[j].get();
+        memcpy(lp.data() + 128 * j, t.data(), 128);
+      }
+      o.point_sum(lp.data(), jobs, 0, lhs_xy, &lhs_inf);
+      const bool same = (lhs_inf != 0) == (rhs_inf != 0) && (lhs_inf || memcmp(lhs_xy, rhs_xy, 64) == 0);
+      *verdict = same ? 0u : (uint32_t)NMX_IPA_REJECT;
+      if (out_ck_hat_xy64) memcpy(out_ck_hat_xy64, ck_hat, 64);
+      if (out_ck_hat_is_inf) *out_ck_hat_is_inf = ck_hat_inf;
+      if (out_b_hat) memcpy(out_b_hat, b_hat, 32);
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);  // nothing of this call still reads the caller's vector
+      throw;
+    }
+  });
+}
+
 int nmx_r1cs_cross_term(uint64_t hA, uint64_t hB, uint64_t hC, const void* z1, const void* z2, size_t z_len, const void* e,
                         const void* u, uint32_t flags, void* out) {
   return guarded([&] {

@@ -741,6 +741,15 @@ void fv_ipa_round(Ctx&, int field, const uint32_t* a, const uint32_t* b, const u
                   const uint32_t** partial_host);
 void fv_ipa_scalar(int field, const uint32_t* partial_host, size_t n, int which, uint32_t flags, uint8_t* out32);
 void fv_ipa_last(Ctx&, int field, const uint32_t* a, const void* r, const void* rinv, uint32_t flags, uint32_t* dout, uint8_t* out32);
+// inner-product argument, the verifier's field side (ipa_verify.hpp): range / zero checks of the challenges (NMX_E_SCALAR_RANGE, NMX_E_ZERO),
+// r^2 and r^-2 in the ABI form (32 ell bytes each), with `point` the closed form of b_hat; then ONE launch writes s[lo, lo + cnt) (canonical
+// integers) and, with b_dev (the range's piece), the block partials of <b, s> into pinned host memory -- fv_ipa_verify_bhat adds them up
+// once the stream has been waited for
+void fv_ipa_verify_s(Ctx&, int field, const void* rs, uint32_t ell, const void* point, uint32_t flags, uint64_t lo, uint64_t cnt,
+                     uint32_t* s_out, const uint32_t* b_dev, uint8_t* rsq_abi, uint8_t* rinvsq_abi, uint8_t* bhat_point,
+                     const uint32_t** partial_host, uint32_t* blocks);
+void fv_ipa_verify_bhat(int field, const uint32_t* partial_host, uint32_t blocks, uint32_t flags, uint8_t* out32);
+void fv_field_mul_host(int field, const void* a, const void* b, uint32_t flags, uint8_t* out32);  // a * b, ABI form, NMX_E_SCALAR_RANGE
 void fv_ipa_one(Ctx&, int field, uint32_t* S);
 bool fv_ipa_invert(int field, const void* r, uint32_t flags, void* out);
 void fv_plain_sums(Ctx&, int field, int kind, const void* A, const void* B, const void* C, size_t len, uint32_t flags,

@@ -883,3 +883,4 @@ void fv_eq_sums(Ctx& c, int field, int mode, const void* A, const void* B, const
 
 #include "sumcheck_prove.hpp"
 #include "ipa.hpp"
+#include "ipa_verify.hpp"

@@ -516,3 +516,43 @@ def ipa_prove(ck, ck_c_xy64, a, b, transcript, mont=False, ctx=None):
     Lb, Rb = oL.tobytes(), oR.tobytes()
     return ([Lb[64 * j: 64 * j + 64] for j in range(rounds)], [Rb[64 * j: 64 * j + 64] for j in range(rounds)],
             [(bool(oi[2 * j]), bool(oi[2 * j + 1])) for j in range(rounds)], ah.tobytes())
+
+
+def ipa_verify(ck, ck_c_xy64, comm_a, c, b, L_vec, R_vec, infs, a_hat, rs, mont=False, point=False, want_intermediates=False):
+    """InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) over a registered Pedersen key, from the point where the caller's
+    transcript has produced the round challenges `rs` (32 bytes each, round 0 first).  `comm_a`: a Commitment, (xy64, is_inf) or 64
+    bytes; `c`: U.c; `b`: U.b_vec (host array or CUDA tensor, len a power of two) or, with point=True, the evaluation point (log2(n)
+    elements, most significant variable first: the eq table is never built); L_vec / R_vec / infs / a_hat as ipa_prove returns them
+    (infs may be None).  True iff the proof is accepted; with want_intermediates (accepted, ck_hat as a Commitment, b_hat as 32 bytes)."""
+    if isinstance(comm_a, Commitment):
+        ca_xy, ca_inf = comm_a.xy, comm_a.is_inf
+    elif isinstance(comm_a, tuple):
+        ca_xy, ca_inf = comm_a[0], bool(comm_a[1])
+    else:
+        ca_xy, ca_inf = comm_a, False
+    rounds = len(L_vec)
+    assert len(R_vec) == rounds and len(rs) == rounds, "InvalidInputLength (ipa_pc.rs:297-303)"
+    pb, nb, devb, _kb = _scalar_arg(b, 32)
+    if point:
+        assert not devb and nb == rounds, "the evaluation point is a host array of log2(n) elements"
+        n = 1 << rounds
+    else:
+        n = nb
+    u, ca = _host_u8(ck_c_xy64, 64), _host_u8(bytes(ca_xy), 64)
+    cs, ah = _host_u8(c, 32), _host_u8(a_hat, 32)
+    Lb = _host_u8(b"".join(bytes(x) for x in L_vec) or bytes(64), 64)
+    Rb = _host_u8(b"".join(bytes(x) for x in R_vec) or bytes(64), 64)
+    rb = _host_u8(b"".join(bytes(x) for x in rs) or bytes(32), 32)
+    oi = np.zeros(2 * max(rounds, 1), np.uint8)
+    for j, (li, ri) in enumerate(infs or []):
+        oi[2 * j], oi[2 * j + 1] = int(bool(li)), int(bool(ri))
+    flags = devb | (L.SCALARS_MONT if mont else 0) | (L.BASES_MONT if ck.mont else 0) | (L.IPA_B_IS_POINT if point else 0)
+    verdict = ctypes.c_uint32(0)
+    ckh, ckh_inf, bh = np.zeros(64, np.uint8), np.zeros(1, np.uint8), np.zeros(32, np.uint8)
+    _check(L.lib().nmx_ipa_verify(ck.handle, u.ctypes.data, ca.ctypes.data, int(ca_inf), cs.ctypes.data, pb, n, Lb.ctypes.data,
+                                  Rb.ctypes.data, oi.ctypes.data, ah.ctypes.data, rb.ctypes.data, flags, ctypes.byref(verdict),
+                                  ckh.ctypes.data, ckh_inf.ctypes.data, bh.ctypes.data))
+    ok = verdict.value == 0
+    if want_intermediates:
+        return ok, Commitment(ckh.tobytes(), bool(ckh_inf[0])), bh.tobytes()
+    return ok
