@@ -599,6 +599,31 @@ int nmx_spmv_apply_pair(uint64_t handle, const void* z1, const void* z2, size_t 
  * single-matrix calls.  Host operands: one matrix after the other.  1 <= k <= 8, all matrices over the same field. */
 int nmx_spmv_apply_many(const uint64_t* handles, size_t k, int transposed, const void* x, size_t x_len, uint32_t flags,
                         void* const* outs);
+/* RelaxedR1CSSNARK::verify's multi_evaluate (src/spartan/snark.rs:325-353) as ONE call -- the one piece of CompressedSNARK::verify
+ * that grows with the circuit and is not the evaluation argument:
+ *   out[i] = sum over every entry (row, col, val) of M_i :  T_x[row] * T_y[col] * val,      i < k
+ *   T_x = EqPolynomial::evals_from_points(r_x), T_y = EqPolynomial::evals_from_points(r_y)
+ * which the verifier needs for A, B, C to check claim_inner_final == (evals[0] + r evals[1] + r^2 evals[2]) * eval_Z (snark.rs:355).
+ * One pass over the resident CSR arrays of all k matrices: T_x is never materialised (two sqrt-size tables, one product per row),
+ * T_y is built once in workspace and shared, nothing rows- or cols-sized is written besides it, and the TRANSPOSED form of a
+ * matrix is neither built nor required (a verifier that never proves holds the forward arrays only).
+ *   handles     k matrices from nmx_spmv_register, 1 <= k <= 8, all over one field (the rule of nmx_spmv_apply_many); any other k,
+ *               or matrices over different fields: NMX_E_ARG.  An unknown handle: NMX_E_HANDLE.
+ *   r_x, r_y    ell_x / ell_y elements on the HOST, element 0 the most significant variable (as nmx_eq_evals_from_points), canonical,
+ *               or Montgomery limbs with NMX_SCALARS_MONT -- then out is Montgomery too.  A coordinate >= the modulus:
+ *               NMX_E_SCALAR_RANGE, exactly as nmx_eq_evals_from_points; ell_x, ell_y < 31 as there (NMX_E_ARG).
+ *   shapes      rows <= 2^ell_x and cols <= 2^ell_y for EVERY matrix (the reference indexes T_x[row_idx], T_y[col_idx], snark.rs:336,
+ *               and would panic; it calls with ell_x = log2(num_cons), ell_y = log2(num_vars) + 1 and cols = num_vars + 1 + num_io
+ *               < 2^ell_y).  A violation: NMX_E_ARG, the message names the matrix and the bound.  Matrices of different shapes in
+ *               one call are fine as long as each obeys the rule.  More than 2^24 rows: NMX_E_TOO_LARGE.
+ *   flags       NMX_SCALARS_MONT or 0; any other flag: NMX_E_ARG.  Null handles / out, null r_x with ell_x > 0 (r_y alike): NMX_E_ARG.
+ *   out         k x 32 bytes on the host.  On an error nothing is written.
+ * Every argument check runs before a device is touched or a kernel launched.  Synchronous, ordered behind the calling thread's
+ * NMX_ASYNC calls like every synchronous call; thread-safe and re-entrant (the reference evaluates the three matrices under
+ * into_par_iter, snark.rs:347-350); runs on logical device 0, where matrices live.  The result is exact: it does not depend on
+ * the launch geometry. */
+int nmx_r1cs_evaluate(const uint64_t* handles, size_t k, const void* r_x, size_t ell_x, const void* r_y, size_t ell_y, uint32_t flags,
+                      uint8_t* out /* k x 32 */);
 
 /* ---- measurement ------------------------------------------------------------------------------------
  * With profiling on, every MSM brackets its stages with hipEvents on the stream the kernels run on;

@@ -496,6 +496,18 @@ inline SatResult r1cs_is_sat(const uint64_t mats[3], const CommitmentKey* ck, co
                         &s.verdict, &s.bad_rows, &s.first_bad_row));
   return s;
 }
+// RelaxedR1CSSNARK::verify's multi_evaluate (spartan/snark.rs:325-353) as one call: evals[i] = sum over the entries (row, col, val) of
+// mats[i] of eq(r_x, row) eq(r_y, col) val -- what snark.rs:355 multiplies by eval_Z.  r_x, r_y are host vectors (element 0 the most
+// significant variable) with rows <= 2^r_x.size() and cols <= 2^r_y.size() for every matrix; mont: they, and the result, are
+// Montgomery limbs.  Reads the forward CSR arrays only: no transposed form is built.
+inline std::vector<Scalar> r1cs_evaluate(const uint64_t* mats, size_t k, const std::vector<Scalar>& r_x, const std::vector<Scalar>& r_y,
+                                         bool mont = false) {
+  std::vector<Scalar> out(k ? k : 1);
+  check(nmx_r1cs_evaluate(mats, k, r_x.empty() ? nullptr : r_x[0].data(), r_x.size(), r_y.empty() ? nullptr : r_y[0].data(), r_y.size(),
+                          mont ? NMX_SCALARS_MONT : 0u, out[0].data()));
+  out.resize(k);
+  return out;
+}
 inline Scalar mle_evaluate(int field, const void* z, size_t len, const std::vector<Scalar>& r) {
   Scalar out;
   check(nmx_mle_evaluate(field, z, len, r.data(), r.size(), kDev, out.data()));

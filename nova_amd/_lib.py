@@ -113,6 +113,7 @@ def lib():
     L.nmx_spmv_apply_pair.argtypes = [u64, vp, vp, sz, u32, vp, vp]
     L.nmx_poly_fold_chain.argtypes = [ctypes.c_int, vp, sz, vp, sz, u32, vp]
     L.nmx_spmv_apply_many.argtypes = [vp, sz, ctypes.c_int, vp, sz, u32, vp]
+    L.nmx_r1cs_evaluate.argtypes = [vp, sz, vp, sz, vp, sz, u32, vp]
     L.nmx_sumcheck_plain_sums.argtypes = [i, i, vp, vp, vp, sz, u32, vp]
     L.nmx_poly_eval_multi.argtypes = [i, vp, vp, sz, vp, sz, u32, vp]
     L.nmx_sumcheck_bind_eq_sums.argtypes = [i, i, vp, vp, vp, sz, vp, vp, sz, vp, sz, u32, u32, vp, vp, vp, vp]

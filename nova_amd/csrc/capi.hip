@@ -2586,6 +2586,44 @@ int nmx_spmv_apply_many(const uint64_t* handles, size_t k, int transposed, const
   });
 }
 
+// RelaxedR1CSSNARK::verify's multi_evaluate (src/spartan/snark.rs:325-353) as one call: r1cs_eval.hpp.  Every argument check -- the
+// shapes against the points' lengths included -- comes before the context is leased; the forward CSR arrays are all the pass reads,
+// so the transposed form of a matrix is neither built nor looked at.
+int nmx_r1cs_evaluate(const uint64_t* handles, size_t k, const void* r_x, size_t ell_x, const void* r_y, size_t ell_y, uint32_t flags,
+                      uint8_t* out) {
+  return guarded([&] {
+    require(handles && out && k >= 1 && k <= 8, NMX_E_ARG, "bad argument (1 .. 8 matrices)");
+    require((r_x || ell_x == 0) && (r_y || ell_y == 0), NMX_E_ARG, "null argument");
+    require(!(flags & ~(uint32_t)NMX_SCALARS_MONT), NMX_E_ARG, "unsupported flag");
+    require(ell_x < 31 && ell_y < 31, NMX_E_ARG, "too many variables");
+    std::vector<std::shared_ptr<Global::SparseSet>> sp(k);
+    {
+      std::lock_guard<std::mutex> lk(G.mu);
+      for (size_t i = 0; i < k; i++) {
+        auto it = G.sparse.find(handles[i]);
+        if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
+        sp[i] = it->second;
+      }
+    }
+    std::vector<R1csEvalItem> items(k);
+    for (size_t i = 0; i < k; i++) {
+      const Global::SparseSet& ss = *sp[i];
+      require(ss.field == sp[0]->field, NMX_E_ARG, "matrices over different fields");
+      if (ss.rows > ((size_t)1 << ell_x))
+        throw Fail{NMX_E_ARG, "matrix " + std::to_string(i) + ": " + std::to_string(ss.rows) + " rows > 2^ell_x = " +
+                                  std::to_string((size_t)1 << ell_x) + " (T_x[row_idx], src/spartan/snark.rs:336)"};
+      if (ss.cols > ((size_t)1 << ell_y))
+        throw Fail{NMX_E_ARG, "matrix " + std::to_string(i) + ": " + std::to_string(ss.cols) + " columns > 2^ell_y = " +
+                                  std::to_string((size_t)1 << ell_y) + " (T_y[col_idx], src/spartan/snark.rs:336)"};
+      items[i].indptr = ss.indptr, items[i].indices = ss.indices, items[i].data = ss.data, items[i].rows = ss.rows, items[i].cols = ss.cols;
+    }
+    CtxLease L;  // logical device 0, where matrices live; behind the calling thread's NMX_ASYNC calls
+    uint8_t res[8 * 32];
+    fv_r1cs_evaluate(*L.c, sp[0]->field, items.data(), k, r_x, (uint32_t)ell_x, r_y, (uint32_t)ell_y, flags, res);
+    memcpy(out, res, 32 * k);
+  });
+}
+
 int nmx_field_batch_invert(int field, const void* v, size_t n, uint32_t flags, void* out) {
   return guarded([&] {
     require(field >= 0 && field < 4, NMX_E_ARG, "bad field id");

@@ -720,6 +720,15 @@ void fv_r1cs_cross_term(Ctx&, int field, const uint32_t* const* indptr, const ui
 void fv_r1cs_sat(Ctx&, int field, const uint32_t* const* indptr, const uint32_t* const* indices, const uint32_t* const* data, size_t rows,
                  size_t cols, const void* W, size_t n_w, const void* E, const void* u, const void* X, size_t n_io, uint32_t flags,
                  uint64_t* bad_rows, uint64_t* first_bad_row);
+// RelaxedR1CSSNARK::verify's multi_evaluate (r1cs_eval.hpp): out[j] = sum over the entries of matrix j of T_x[row] T_y[col] val, k <= 8
+// matrices in one pass; r_x / r_y are host arrays in the ABI form of `flags` (NMX_SCALARS_MONT or canonical), out is a host buffer
+// of k x 32 bytes in the same form.  Synchronous.  rows <= 2^ell_x and cols <= 2^ell_y are the caller's to check.
+struct R1csEvalItem {
+  const uint32_t *indptr = nullptr, *indices = nullptr, *data = nullptr;
+  size_t rows = 0, cols = 0;
+};
+void fv_r1cs_evaluate(Ctx&, int field, const R1csEvalItem* items, size_t k, const void* r_x, uint32_t ell_x, const void* r_y,
+                      uint32_t ell_y, uint32_t flags, uint8_t* out);
 void fv_nifs_fold(Ctx&, int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e, const void* r,
                   uint32_t flags, void* w, void* e);
 void fv_eq_evals(Ctx&, int field, const void* r_host, uint32_t ell, uint32_t flags, uint32_t* d_out);

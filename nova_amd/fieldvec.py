@@ -375,6 +375,22 @@ def multiply_vec_many(mats, x, transposed=False, mont=False, async_=False):
     return [o[1] for o in outs]
 
 
+def r1cs_evaluate(mats, r_x, r_y, mont=False):
+    """nmx_r1cs_evaluate: RelaxedR1CSSNARK::verify's multi_evaluate (src/spartan/snark.rs:325-353) as one call --
+    [sum over the entries (row, col, val) of M of eq(r_x, row) eq(r_y, col) val  for M in mats], 32 bytes each (Montgomery limbs with
+    mont=True, like r_x and r_y then).  mats: 1..8 SparseMatrix over one field (what r1cs_is_sat takes for A, B, C); r_x, r_y: host
+    points, most significant variable first, with rows <= 2^len(r_x) and cols <= 2^len(r_y) for every matrix.  The transposed form of
+    a matrix is not built."""
+    import ctypes
+    k = len(mats)
+    hs = (ctypes.c_uint64 * max(k, 1))(*[m.handle for m in mats])
+    rx, ry = _host_u8(r_x, 32), _host_u8(r_y, 32)
+    out = np.zeros((max(k, 1), 32), dtype=np.uint8)
+    _check(L.lib().nmx_r1cs_evaluate(hs, k, rx.ctypes.data if rx.size else None, rx.size // 32, ry.ctypes.data if ry.size else None,
+                                     ry.size // 32, L.SCALARS_MONT if mont else 0, out.ctypes.data))
+    return [out[i].tobytes() for i in range(k)]
+
+
 def suffix_horner(field, f, u, mont=False):
     """out[i] = sum_{k>=i} f[k] u^(k-i): out[0] = poly_eval(f, u) (hyperkzg.rs:1011-1020), out[1:] = the quotient of
     div_by_monomial(f, u) (hyperkzg.rs:961-999)."""
