@@ -10,6 +10,7 @@
 
 #include "runtime.hpp"
 #include "combine.hpp"
+#include "spmv_row.hpp"  // spmv_index_mask
 
 namespace nmx {
 
@@ -2290,9 +2291,8 @@ struct EvalScratch {
   EvalScratch(Ctx& c, int field, const void* r, size_t ell, size_t len, uint32_t flags) {
     s_right = ell / 2;
     s_left = ell - s_right;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    const size_t bl = pad(((size_t)1 << s_left) * 32), br = pad(((size_t)1 << s_right) * 32);
-    const size_t bz = (flags & NMX_SCALARS_DEVICE) ? 0 : pad(len * 32);
+    const size_t bl = pad256(((size_t)1 << s_left) * 32), br = pad256(((size_t)1 << s_right) * 32);
+    const size_t bz = (flags & NMX_SCALARS_DEVICE) ? 0 : pad256(len * 32);
     aux_reserve(c, bl + br + bz);
     eqL = (uint32_t*)c.aux;
     eqR = (uint32_t*)(c.aux + bl);
@@ -2392,6 +2392,33 @@ int nmx_mle_multi_evaluate(int field, const void* const* zs, size_t k, size_t le
   });
 }
 
+// A registered matrix by handle: the reference keeps it alive under a concurrent nmx_spmv_unregister
+static std::shared_ptr<Global::SparseSet> sparse_ref(uint64_t handle) {
+  std::lock_guard<std::mutex> lk(G.mu);
+  auto it = G.sparse.find(handle);
+  if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
+  return it->second;
+}
+// k of them under one lock; all over one field, and (same_shape: A, B, C of an R1CS instance) of one shape
+static std::vector<std::shared_ptr<Global::SparseSet>> sparse_refs(const uint64_t* handles, size_t k, bool same_shape = false) {
+  std::vector<std::shared_ptr<Global::SparseSet>> sp(k);
+  {
+    std::lock_guard<std::mutex> lk(G.mu);
+    for (size_t i = 0; i < k; i++) {
+      auto it = G.sparse.find(handles[i]);
+      if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
+      sp[i] = it->second;
+    }
+  }
+  for (size_t i = 1; i < k; i++) {
+    if (same_shape)
+      require(sp[i]->field == sp[0]->field && sp[i]->rows == sp[0]->rows && sp[i]->cols == sp[0]->cols, NMX_E_ARG,
+              "A, B, C must share field and shape");
+    else require(sp[i]->field == sp[0]->field, NMX_E_ARG, "matrices over different fields");
+  }
+  return sp;
+}
+
 int nmx_spmv_register(int field, const uint64_t* indptr, const uint64_t* indices, const void* data, size_t rows,
                       size_t cols, uint32_t flags, uint64_t* handle) {
   return guarded([&] {
@@ -2442,18 +2469,12 @@ int nmx_spmv_unregister(uint64_t handle) {
 int nmx_spmv_apply(uint64_t handle, const void* z, size_t z_len, uint32_t flags, void* out) {
   return guarded([&] {
     require(z && out, NMX_E_ARG, "null argument");
-    std::shared_ptr<Global::SparseSet> sp;
-    {
-      std::lock_guard<std::mutex> lk(G.mu);
-      auto it = G.sparse.find(handle);
-      if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
-      sp = it->second;
-    }
+    const auto sp = sparse_ref(handle);
     const Global::SparseSet& ss = *sp;
     require(z_len == ss.cols, NMX_E_ARG, "invalid shape");  // assert_eq!(self.cols, vector.len(), "invalid shape")
     if (ss.rows == 0) return;
     CtxLease L;
-    fv_spmv_apply(*L.c, ss.field, ss.indptr, ss.indices, ss.data, ss.rows, ss.cols, z, flags, out);
+    fv_spmv_apply(*L.c, ss.field, ss.view(), z, flags, out);
   });
 }
 
@@ -2471,8 +2492,7 @@ static std::shared_ptr<Global::SparseSet::Transposed> transposed_of(Ctx& c, Glob
     HIPCHK(hipMemcpyAsync(dt.data(), ss.data, nnz * 32, hipMemcpyDeviceToHost, c.stream));
   }
   HIPCHK(hipStreamSynchronize(c.stream));
-  const bool tagged_in = cols <= ((size_t)1 << 28), tagged_out = rows <= ((size_t)1 << 28);
-  const uint32_t cmask = tagged_in ? (1u << 28) - 1u : 0xffffffffu;
+  const uint32_t cmask = spmv_index_mask(cols), rmask = spmv_index_mask(rows);
   std::vector<uint32_t> cnt(cols + 1, 0);
   for (size_t k = 0; k < nnz; k++) cnt[(ix[k] & cmask) + 1]++;
   for (size_t j = 0; j < cols; j++) cnt[j + 1] += cnt[j];
@@ -2480,8 +2500,8 @@ static std::shared_ptr<Global::SparseSet::Transposed> transposed_of(Ctx& c, Glob
   std::vector<uint8_t> tdt((nnz ? nnz : 1) * 32);
   for (size_t r = 0; r < rows; r++)
     for (uint32_t k = ip[r]; k < ip[r + 1]; k++) {
-      const uint32_t col = ix[k] & cmask, cls = tagged_in ? ix[k] >> 28 : 0u, q = pos[col]++;
-      tix[q] = (uint32_t)r | (tagged_out ? cls << 28 : 0u);  // the class rides along (same coefficient); none if rows need all 32 bits
+      const uint32_t col = ix[k] & cmask, cls = ix[k] & ~cmask, q = pos[col]++;
+      tix[q] = (uint32_t)r | (cls & ~rmask);  // the class bits ride along (same coefficient); none if rows need all 32 bits
       memcpy(tdt.data() + 32 * (size_t)q, dt.data() + 32 * (size_t)k, 32);
     }
   std::vector<uint32_t> vptr{0}, vout, hrow, hstart{0};
@@ -2526,38 +2546,22 @@ static std::shared_ptr<Global::SparseSet::Transposed> transposed_of(Ctx& c, Glob
 int nmx_spmv_apply_transposed(uint64_t handle, const void* x, size_t x_len, uint32_t flags, void* out) {
   return guarded([&] {
     require(x && out, NMX_E_ARG, "null argument");
-    std::shared_ptr<Global::SparseSet> sp;
-    {
-      std::lock_guard<std::mutex> lk(G.mu);
-      auto it = G.sparse.find(handle);
-      if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
-      sp = it->second;
-    }
+    const auto sp = sparse_ref(handle);
     Global::SparseSet& ss = *sp;
     require(x_len == ss.rows, NMX_E_ARG, "invalid shape");  // assert_eq!(rx.len(), S.num_cons()), spartan/mod.rs:504
     if (ss.cols == 0) return;
     CtxLease L;
     auto tr = transposed_of(*L.c, ss);
-    fv_spmv_apply_transposed(*L.c, ss.field, tr->vptr, tr->indices, tr->data, tr->vout, tr->hrow, tr->hstart, tr->nvirt, tr->nheavy,
-                             tr->nparts, ss.rows, ss.cols, x, flags, out);
+    fv_spmv_apply_transposed(*L.c, ss.field, tr->view(ss), x, flags, out);
   });
 }
 
 int nmx_spmv_apply_many(const uint64_t* handles, size_t k, int transposed, const void* x, size_t x_len, uint32_t flags, void* const* outs) {
   return guarded([&] {
     require(handles && x && outs && k >= 1 && k <= 8, NMX_E_ARG, "bad argument (1 .. 8 matrices)");
-    std::vector<std::shared_ptr<Global::SparseSet>> sp(k);
-    {
-      std::lock_guard<std::mutex> lk(G.mu);
-      for (size_t i = 0; i < k; i++) {
-        auto it = G.sparse.find(handles[i]);
-        if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
-        sp[i] = it->second;
-      }
-    }
+    const auto sp = sparse_refs(handles, k);
     for (size_t i = 0; i < k; i++) {
       require(outs[i], NMX_E_ARG, "null output");
-      require(sp[i]->field == sp[0]->field, NMX_E_ARG, "matrices over different fields");
       require(x_len == (transposed ? sp[i]->rows : sp[i]->cols), NMX_E_ARG, "invalid shape");
     }
     if (!(flags & NMX_SCALARS_DEVICE)) {  // host operands: one matrix after the other through the single-matrix paths
@@ -2571,16 +2575,9 @@ int nmx_spmv_apply_many(const uint64_t* handles, size_t k, int transposed, const
     std::vector<std::shared_ptr<Global::SparseSet::Transposed>> tr(k);
     std::vector<SpmvManyItem> items(k);
     for (size_t i = 0; i < k; i++) {
-      Global::SparseSet& ss = *sp[i];
-      SpmvManyItem& m = items[i];
-      m.rows = ss.rows, m.cols = ss.cols, m.out = outs[i];
-      if (transposed) {
-        tr[i] = transposed_of(*L.c, ss);
-        m.vptr = tr[i]->vptr, m.tix = tr[i]->indices, m.tdata = tr[i]->data, m.vout = tr[i]->vout, m.hrow = tr[i]->hrow, m.hstart = tr[i]->hstart;
-        m.nvirt = tr[i]->nvirt, m.nheavy = tr[i]->nheavy, m.nparts = tr[i]->nparts;
-      } else {
-        m.indptr = ss.indptr, m.indices = ss.indices, m.data = ss.data;
-      }
+      items[i].out = outs[i];
+      if (transposed) items[i].tr = (tr[i] = transposed_of(*L.c, *sp[i]))->view(*sp[i]);
+      else items[i].fwd = sp[i]->view();
     }
     fv_spmv_many(*L.c, sp[0]->field, items.data(), k, transposed != 0, x, flags);
   });
@@ -2596,30 +2593,21 @@ int nmx_r1cs_evaluate(const uint64_t* handles, size_t k, const void* r_x, size_t
     require((r_x || ell_x == 0) && (r_y || ell_y == 0), NMX_E_ARG, "null argument");
     require(!(flags & ~(uint32_t)NMX_SCALARS_MONT), NMX_E_ARG, "unsupported flag");
     require(ell_x < 31 && ell_y < 31, NMX_E_ARG, "too many variables");
-    std::vector<std::shared_ptr<Global::SparseSet>> sp(k);
-    {
-      std::lock_guard<std::mutex> lk(G.mu);
-      for (size_t i = 0; i < k; i++) {
-        auto it = G.sparse.find(handles[i]);
-        if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
-        sp[i] = it->second;
-      }
-    }
-    std::vector<R1csEvalItem> items(k);
+    const auto sp = sparse_refs(handles, k);
+    std::vector<CsrView> mats(k);
     for (size_t i = 0; i < k; i++) {
       const Global::SparseSet& ss = *sp[i];
-      require(ss.field == sp[0]->field, NMX_E_ARG, "matrices over different fields");
       if (ss.rows > ((size_t)1 << ell_x))
         throw Fail{NMX_E_ARG, "matrix " + std::to_string(i) + ": " + std::to_string(ss.rows) + " rows > 2^ell_x = " +
                                   std::to_string((size_t)1 << ell_x) + " (T_x[row_idx], src/spartan/snark.rs:336)"};
       if (ss.cols > ((size_t)1 << ell_y))
         throw Fail{NMX_E_ARG, "matrix " + std::to_string(i) + ": " + std::to_string(ss.cols) + " columns > 2^ell_y = " +
                                   std::to_string((size_t)1 << ell_y) + " (T_y[col_idx], src/spartan/snark.rs:336)"};
-      items[i].indptr = ss.indptr, items[i].indices = ss.indices, items[i].data = ss.data, items[i].rows = ss.rows, items[i].cols = ss.cols;
+      mats[i] = ss.view();
     }
     CtxLease L;  // logical device 0, where matrices live; behind the calling thread's NMX_ASYNC calls
     uint8_t res[8 * 32];
-    fv_r1cs_evaluate(*L.c, sp[0]->field, items.data(), k, r_x, (uint32_t)ell_x, r_y, (uint32_t)ell_y, flags, res);
+    fv_r1cs_evaluate(*L.c, sp[0]->field, mats.data(), k, r_x, (uint32_t)ell_x, r_y, (uint32_t)ell_y, flags, res);
     memcpy(out, res, 32 * k);
   });
 }
@@ -2749,6 +2737,36 @@ int nmx_sumcheck_prove_batch_eval(int field, const void* claims, const size_t* n
   });
 }
 
+// Device state of one call that has to outlive the MSMs the call runs (they re-carve the context's arena): the context's aux buffer
+// up to kAuxMax bytes, an allocation of the call's own above that; carved front to back.  `ev`, if the call creates it, goes with it.
+struct CallScratch {
+  static constexpr size_t kAuxMax = (size_t)64 << 20;
+  char* base = nullptr;
+  void* owned = nullptr;
+  size_t used = 0;
+  hipEvent_t ev = nullptr;
+  CallScratch(Ctx& c, size_t total) {
+    if (total <= kAuxMax) {
+      aux_reserve(c, total);
+      base = c.aux;
+    } else {
+      HIPCHK(hipMalloc(&owned, total));
+      base = (char*)owned;
+    }
+  }
+  CallScratch(const CallScratch&) = delete;
+  CallScratch& operator=(const CallScratch&) = delete;
+  ~CallScratch() {
+    if (owned) (void)hipFree(owned);
+    if (ev) (void)hipEventDestroy(ev);
+  }
+  uint32_t* carve(size_t bytes) {
+    char* q = base + used;
+    used += bytes;
+    return (uint32_t*)q;
+  }
+};
+
 // InnerProductArgument::prove (src/provider/ipa_pc.rs:174-281) as one call.  The commitment key is never folded (ipa.hpp): every
 // round's L and R are one fused two-vector commitment over the registered key, whose window tables are the ones every other
 // commitment of that curve uses.  Per round: k_ipa_expand (+ the one-block partial sum) -> 64 bytes to the host (c_L, c_R) ->
@@ -2782,46 +2800,24 @@ int nmx_ipa_prove(uint64_t ck_handle, const void* ck_c_xy64, const void* a, cons
       return;
     }
     // the call's device state, outside the arena the MSMs re-carve: [a b staged] A0 A1 B0 B1 vL vR S0 S1 dout
-    auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t half = pad((n / 2) * 32), full = pad(n * 32);
+    const size_t half = pad256((n / 2) * 32), full = pad256(n * 32);
     const size_t total = (dev ? 0 : 2 * full) + 4 * half + 2 * full + 2 * half + 256;
-    struct Own {
-      void* p = nullptr;
-      hipEvent_t ev = nullptr;
-      ~Own() {
-        if (p) (void)hipFree(p);
-        if (ev) (void)hipEventDestroy(ev);
-      }
-    } own;
-    char* base;
-    if (total <= ((size_t)64 << 20)) {
-      aux_reserve(c, total);
-      base = c.aux;
-    } else {
-      HIPCHK(hipMalloc(&own.p, total));
-      base = (char*)own.p;
-    }
+    CallScratch own(c, total);
     HIPCHK(hipEventCreateWithFlags(&own.ev, hipEventDisableTiming));
-    size_t used = 0;
-    auto carve = [&](size_t bytes) {
-      char* q = base + used;
-      used += bytes;
-      return (uint32_t*)q;
-    };
     const uint32_t *a_cur, *b_cur;
     if (dev) {
       a_cur = (const uint32_t*)a, b_cur = (const uint32_t*)b;
     } else {
-      uint32_t *sa = carve(full), *sb = carve(full);
+      uint32_t *sa = own.carve(full), *sb = own.carve(full);
       HIPCHK(hipMemcpyAsync(sa, a, n * 32, hipMemcpyHostToDevice, c.stream));
       HIPCHK(hipMemcpyAsync(sb, b, n * 32, hipMemcpyHostToDevice, c.stream));
       a_cur = sa, b_cur = sb;
     }
-    uint32_t* A[2] = {carve(half), carve(half)};
-    uint32_t* B[2] = {carve(half), carve(half)};
-    uint32_t *vL = carve(full), *vR = carve(full);
-    uint32_t* S[2] = {carve(half), carve(half)};
-    uint32_t* dout = carve(256);
+    uint32_t* A[2] = {own.carve(half), own.carve(half)};
+    uint32_t* B[2] = {own.carve(half), own.carve(half)};
+    uint32_t *vL = own.carve(full), *vR = own.carve(full);
+    uint32_t* S[2] = {own.carve(half), own.carve(half)};
+    uint32_t* dout = own.carve(256);
     try {
       const bool sharded = !bs->parts.empty();
       const BaseSet& key = sharded ? *bs : prefix_or_key(*bs, 0, n);
@@ -2921,23 +2917,9 @@ int nmx_ipa_verify(uint64_t ck_handle, const void* ck_c_xy64, const void* comm_a
     fv_field_mul_host(field, a_hat, c_sc, sflags, ab);  // (the range check of a_hat and c, before anything is started)
     CtxLease L;
     Ctx& c = *L.c;
-    auto pad = [](size_t x) { return (x + 255) & ~(size_t)255; };
-    const size_t full = pad(n * 32), total = full + ((point || dev) ? 0 : full);
-    struct Own {
-      void* p = nullptr;
-      ~Own() {
-        if (p) (void)hipFree(p);
-      }
-    } own;
-    char* base;
-    if (total <= ((size_t)64 << 20)) {
-      aux_reserve(c, total);
-      base = c.aux;
-    } else {
-      HIPCHK(hipMalloc(&own.p, total));
-      base = (char*)own.p;
-    }
-    uint32_t* s_dev = (uint32_t*)base;
+    const size_t full = pad256(n * 32), total = full + ((point || dev) ? 0 : full);
+    CallScratch own(c, total);
+    uint32_t* s_dev = own.carve(full);
     const uint32_t* b_dev = nullptr;
     std::vector<uint8_t> rsq(32 * (size_t)ell + 32), rinvsq(32 * (size_t)ell + 32);
     uint8_t b_hat[32], ck_hat[64] = {}, ck_hat_inf = 0;
@@ -2946,8 +2928,9 @@ int nmx_ipa_verify(uint64_t ck_handle, const void* ck_c_xy64, const void* comm_a
         if (dev) {
           b_dev = (const uint32_t*)b;
         } else {
-          HIPCHK(hipMemcpyAsync(base + full, b, n * 32, hipMemcpyHostToDevice, c.stream));
-          b_dev = (const uint32_t*)(base + full);
+          uint32_t* staged = own.carve(full);
+          HIPCHK(hipMemcpyAsync(staged, b, n * 32, hipMemcpyHostToDevice, c.stream));
+          b_dev = staged;
         }
       }
       const uint32_t* partial_host = nullptr;
@@ -3010,26 +2993,13 @@ int nmx_r1cs_cross_term(uint64_t hA, uint64_t hB, uint64_t hC, const void* z1, c
   return guarded([&] {
     require(z1 && e && u && out, NMX_E_ARG, "null argument");
     require(flags & NMX_SCALARS_DEVICE, NMX_E_ARG, "nmx_r1cs_cross_term works on HBM-resident vectors");
-    std::shared_ptr<Global::SparseSet> sp[3];
-    {
-      std::lock_guard<std::mutex> lk(G.mu);
-      const uint64_t hs[3] = {hA, hB, hC};
-      for (int j = 0; j < 3; j++) {
-        auto it = G.sparse.find(hs[j]);
-        if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
-        sp[j] = it->second;
-      }
-    }
-    for (int j = 0; j < 3; j++)
-      require(sp[j]->field == sp[0]->field && sp[j]->rows == sp[0]->rows && sp[j]->cols == sp[0]->cols, NMX_E_ARG,
-              "A, B, C must share field and shape");
+    const uint64_t hs[3] = {hA, hB, hC};
+    const auto sp = sparse_refs(hs, 3, /*same_shape=*/true);
+    const CsrView abc[3] = {sp[0]->view(), sp[1]->view(), sp[2]->view()};
     require(z_len == sp[0]->cols, NMX_E_ARG, "invalid shape");
     if (sp[0]->rows == 0) return;
-    const uint32_t* ip[3] = {sp[0]->indptr, sp[1]->indptr, sp[2]->indptr};
-    const uint32_t* ix[3] = {sp[0]->indices, sp[1]->indices, sp[2]->indices};
-    const uint32_t* dt[3] = {sp[0]->data, sp[1]->data, sp[2]->data};
     CtxLease L;
-    fv_r1cs_cross_term(*L.c, sp[0]->field, ip, ix, dt, sp[0]->rows, sp[0]->cols, z1, z2, e, u, flags, out);
+    fv_r1cs_cross_term(*L.c, sp[0]->field, abc, z1, z2, e, u, flags, out);
   });
 }
 
@@ -3048,19 +3018,9 @@ int nmx_r1cs_is_sat(uint64_t hA, uint64_t hB, uint64_t hC, uint64_t ck_handle, c
     require((E == nullptr) == (u == nullptr), NMX_E_ARG, "E and u go together: both for is_sat_relaxed, neither for is_sat");
     const bool relaxed = E != nullptr;
     require((W || n_w == 0) && (X || n_io == 0), NMX_E_ARG, "null argument");
-    std::shared_ptr<Global::SparseSet> sp[3];
-    {
-      std::lock_guard<std::mutex> lk(G.mu);
-      const uint64_t hs[3] = {hA, hB, hC};
-      for (int j = 0; j < 3; j++) {
-        auto it = G.sparse.find(hs[j]);
-        if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
-        sp[j] = it->second;
-      }
-    }
-    for (int j = 0; j < 3; j++)
-      require(sp[j]->field == sp[0]->field && sp[j]->rows == sp[0]->rows && sp[j]->cols == sp[0]->cols, NMX_E_ARG,
-              "A, B, C must share field and shape");
+    const uint64_t hs[3] = {hA, hB, hC};
+    const auto sp = sparse_refs(hs, 3, /*same_shape=*/true);
+    const CsrView abc[3] = {sp[0]->view(), sp[1]->view(), sp[2]->view()};
     const size_t rows = sp[0]->rows, cols = sp[0]->cols;
     require(n_w <= cols && n_io <= cols && n_w + 1 + n_io == cols, NMX_E_ARG,
             "W.len() + 1 + X.len() != number of columns (W.len() != num_vars or X.len() != num_io, src/r1cs/mod.rs:489-494)");
@@ -3091,12 +3051,8 @@ int nmx_r1cs_is_sat(uint64_t hA, uint64_t hB, uint64_t hC, uint64_t ck_handle, c
       pc[0] = start_commit(bs, W, n_w, h_xy64, r_W, cflags);
       if (relaxed) pc[1] = start_commit(bs, E, n_e, h_xy64, r_E, cflags);
     }
-    const uint32_t* ip[3] = {sp[0]->indptr, sp[1]->indptr, sp[2]->indptr};
-    const uint32_t* ix[3] = {sp[0]->indices, sp[1]->indices, sp[2]->indices};
-    const uint32_t* dt[3] = {sp[0]->data, sp[1]->data, sp[2]->data};
     uint64_t nbad = 0, first = ~0ull;
-    fv_r1cs_sat(*L.c, sp[0]->field, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags & (NMX_SCALARS_MONT | NMX_SCALARS_DEVICE), &nbad,
-                &first);
+    fv_r1cs_sat(*L.c, sp[0]->field, abc, W, n_w, E, u, X, n_io, flags & (NMX_SCALARS_MONT | NMX_SCALARS_DEVICE), &nbad, &first);
     uint32_t v = nbad ? (uint32_t)NMX_UNSAT_EQ : 0u;
     PendingCommit::Res res[2];
     for (int j = 0; j < 2; j++)
@@ -3129,18 +3085,12 @@ int nmx_spmv_apply_pair(uint64_t handle, const void* z1, const void* z2, size_t 
                         void* out2) {
   return guarded([&] {
     require(z1 && z2 && out1 && out2, NMX_E_ARG, "null argument");
-    std::shared_ptr<Global::SparseSet> sp;
-    {
-      std::lock_guard<std::mutex> lk(G.mu);
-      auto it = G.sparse.find(handle);
-      if (it == G.sparse.end()) throw Fail{NMX_E_HANDLE, "unknown matrix handle"};
-      sp = it->second;
-    }
+    const auto sp = sparse_ref(handle);
     const Global::SparseSet& ss = *sp;
     require(z_len == ss.cols, NMX_E_ARG, "invalid shape for v1 / v2");  // sparse.rs:217-218
     if (ss.rows == 0) return;
     CtxLease L;
-    fv_spmv_apply_pair(*L.c, ss.field, ss.indptr, ss.indices, ss.data, ss.rows, ss.cols, z1, z2, flags, out1, out2);
+    fv_spmv_apply_pair(*L.c, ss.field, ss.view(), z1, z2, flags, out1, out2);
   });
 }
 

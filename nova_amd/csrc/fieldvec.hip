@@ -972,19 +972,19 @@ struct VecIO {  // stages host vectors through the context arena; device vectors
   std::vector<std::pair<void*, const void*>> outs;  // (device, host)
   VecIO(Ctx& ctx, uint32_t flags, size_t n_, int n_vecs)
       : c(ctx), dev((flags & NMX_SCALARS_DEVICE) != 0), async((flags & NMX_ASYNC) && (flags & NMX_SCALARS_DEVICE)), n(n_) {
-    if (!dev) arena_reserve(c, (size_t)n_vecs * ((n * 32 + 255) & ~(size_t)255) + 256);
+    if (!dev) arena_reserve(c, (size_t)n_vecs * pad256(n * 32) + 256);
   }
   const uint32_t* in(const void* p, size_t elems) {
     if (dev) return (const uint32_t*)p;
     char* d = c.arena + used;
-    used += (elems * 32 + 255) & ~(size_t)255;
+    used += pad256(elems * 32);
     HIPCHK(hipMemcpyAsync(d, p, elems * 32, hipMemcpyHostToDevice, c.stream));
     return (const uint32_t*)d;
   }
   uint32_t* out(void* p, size_t elems) {
     if (dev) return (uint32_t*)p;
     char* d = c.arena + used;
-    used += (elems * 32 + 255) & ~(size_t)255;
+    used += pad256(elems * 32);
     outs.push_back({d, p});
     out_elems = elems;
     return (uint32_t*)d;
@@ -1102,10 +1102,9 @@ template <int FID> static void eq_evals_t(Ctx& c, const void* r_host, uint32_t e
   }
   if (ell <= 2 * EqDirectFn<FID>::kMaxEll) {  // two sqrt-size tables + one product per entry (EqSplit2Fn / EqProductFn)
     const uint32_t ellR = ell / 2, ellL = ell - ellR;
-    auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-    arena_reserve(c, pad(((size_t)1 << ellL) * 32) + pad(((size_t)1 << ellR) * 32) + 256);
+    arena_reserve(c, pad256(((size_t)1 << ellL) * 32) + pad256(((size_t)1 << ellR) * 32) + 256);
     EqSplit2Fn<FID> f;
-    f.outL = (uint32_t*)c.arena, f.outR = (uint32_t*)(c.arena + pad(((size_t)1 << ellL) * 32));
+    f.outL = (uint32_t*)c.arena, f.outR = (uint32_t*)(c.arena + pad256(((size_t)1 << ellL) * 32));
     f.ellL = ellL, f.ellR = ellR, f.oneL = F::one(), f.oneR = F::from_words(w);
     const F one_i = F::one();
     for (uint32_t i = 0; i < 2 * EqDirectFn<FID>::kMaxEll; i++) f.r[i] = f.nr[i] = F::zero();
@@ -1179,39 +1178,35 @@ template <int FID> static void spmv_classify_t(Ctx& c, const uint32_t* d_data, u
   be.launch(f, (uint32_t)nnz);
 }
 template <int FID>
-static void spmv_apply_t(Ctx& c, const uint32_t* indptr, const uint32_t* indices, const uint32_t* data, size_t rows,
-                         size_t cols, const void* z, uint32_t flags, void* out) {
-  VecIO io(c, flags, rows + cols, 2);
-  const uint32_t* dz = io.in(z, cols);
-  uint32_t* dout = io.out(out, rows);
-  SpmvFn<FID> f{indptr, indices, data, dz, dout, cols <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu};
-  timed_launch(c, f, rows, &io);
+static void spmv_apply_t(Ctx& c, const CsrView& m, const void* z, uint32_t flags, void* out) {
+  VecIO io(c, flags, m.rows + m.cols, 2);
+  const uint32_t* dz = io.in(z, m.cols);
+  uint32_t* dout = io.out(out, m.rows);
+  SpmvFn<FID> f{m.indptr, m.indices, m.data, dz, dout, spmv_index_mask(m.cols)};
+  timed_launch(c, f, m.rows, &io);
 }
 
-// x: rows of M; out: cols of M.  tr_*: the virtual-row form of M^T (capi.hip builds it).
-template <int FID>
-static void spmv_apply_transposed_t(Ctx& c, const uint32_t* vptr, const uint32_t* indices, const uint32_t* data, const uint32_t* vout,
-                                    const uint32_t* hrow, const uint32_t* hstart, size_t nvirt, size_t nheavy, size_t nparts, size_t rows,
-                                    size_t cols, const void* x, uint32_t flags, void* out) {
+// x: rows of M; out: cols of M.  t: the virtual-row form of M^T (capi.hip builds it).
+template <int FID> static void spmv_apply_transposed_t(Ctx& c, const CsrTransposedView& t, const void* x, uint32_t flags, void* out) {
+  const size_t rows = t.rows, cols = t.cols;
   const bool dev = (flags & NMX_SCALARS_DEVICE) != 0, async = dev && (flags & NMX_ASYNC);
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  const size_t pb = pad((nparts ? nparts : 1) * 32);
-  arena_reserve(c, pb + (dev ? 0 : pad(rows * 32) + pad(cols * 32)) + 256);
+  const size_t pb = pad256((t.nparts ? t.nparts : 1) * 32);
+  arena_reserve(c, pb + (dev ? 0 : pad256(rows * 32) + pad256(cols * 32)) + 256);
   uint32_t* partial = (uint32_t*)c.arena;
   const uint32_t* dx = (const uint32_t*)x;
   uint32_t* dout = (uint32_t*)out;
   if (!dev) {
     HIPCHK(hipMemcpyAsync(c.arena + pb, x, rows * 32, hipMemcpyHostToDevice, c.stream));
     dx = (const uint32_t*)(c.arena + pb);
-    dout = (uint32_t*)(c.arena + pb + pad(rows * 32));
+    dout = (uint32_t*)(c.arena + pb + pad256(rows * 32));
   }
   const bool prof = G.profiling;
   DeviceBackend be(c, false, prof);
   be.mark("kernel");
-  SpmvSegFn<FID> f{vptr, indices, data, dx, vout, dout, partial, rows <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu};
-  be.launch(f, (uint32_t)nvirt);
-  if (nheavy) {
-    hipLaunchKernelGGL((k_spmv_heavy<FID>), dim3((uint32_t)nheavy), dim3(256), 0, c.stream, hrow, hstart, (const uint32_t*)partial, dout);
+  SpmvSegFn<FID> f{t.vptr, t.indices, t.data, dx, t.vout, dout, partial, spmv_index_mask(rows)};
+  be.launch(f, (uint32_t)t.nvirt);
+  if (t.nheavy) {
+    hipLaunchKernelGGL((k_spmv_heavy<FID>), dim3((uint32_t)t.nheavy), dim3(256), 0, c.stream, t.hrow, t.hstart, (const uint32_t*)partial, dout);
     HIPCHK(hipGetLastError());
   }
   be.mark("end");
@@ -1229,23 +1224,23 @@ static void spmv_apply_transposed_t(Ctx& c, const uint32_t* vptr, const uint32_t
 }
 
 template <int FID>
-static void spmv_apply_pair_t(Ctx& c, const uint32_t* indptr, const uint32_t* indices, const uint32_t* data, size_t rows,
-                              size_t cols, const void* z1, const void* z2, uint32_t flags, void* out1, void* out2) {
-  VecIO io(c, flags, rows + cols, 4);
-  const uint32_t* d1 = io.in(z1, cols);
-  const uint32_t* d2 = io.in(z2, cols);
-  uint32_t* o1 = io.out(out1, rows);
-  uint32_t* o2 = io.out(out2, rows);
-  SpmvPairFn<FID> f{indptr, indices, data, d1, d2, o1, o2, cols <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu};
-  timed_launch(c, f, rows, &io);
+static void spmv_apply_pair_t(Ctx& c, const CsrView& m, const void* z1, const void* z2, uint32_t flags, void* out1, void* out2) {
+  VecIO io(c, flags, m.rows + m.cols, 4);
+  const uint32_t* d1 = io.in(z1, m.cols);
+  const uint32_t* d2 = io.in(z2, m.cols);
+  uint32_t* o1 = io.out(out1, m.rows);
+  uint32_t* o2 = io.out(out2, m.rows);
+  SpmvPairFn<FID> f{m.indptr, m.indices, m.data, d1, d2, o1, o2, spmv_index_mask(m.cols)};
+  timed_launch(c, f, m.rows, &io);
 }
 
 // commit_T's chain (src/r1cs/mod.rs:590-620) on HBM-resident vectors: Z = z1 + z2 (z2 may be null: Z = z1), then SpmvCrossFn.
 // Z lives in the context arena; with NMX_ASYNC nothing waits (the arena is only re-carved by later calls on the same stream).
 template <int FID>
-static void r1cs_cross_term_t(Ctx& c, const uint32_t* const* ip, const uint32_t* const* ix, const uint32_t* const* dt, size_t rows,
-                              size_t cols, const void* z1, const void* z2, const void* e, const void* u, uint32_t flags, void* out) {
+static void r1cs_cross_term_t(Ctx& c, const CsrView (&m)[3], const void* z1, const void* z2, const void* e, const void* u, uint32_t flags,
+                              void* out) {
   using F = Fp<FID>;
+  const size_t rows = m[0].rows, cols = m[0].cols;
   const bool mont = flags & NMX_SCALARS_MONT;
   VecIO io(c, flags, rows, 0);
   const uint32_t* dz = (const uint32_t*)z1;
@@ -1259,20 +1254,19 @@ static void r1cs_cross_term_t(Ctx& c, const uint32_t* const* ip, const uint32_t*
   }
   const F k = mont ? F::from_limbs(FpParams<FID>::C266) : F::from_limbs(FpParams<FID>::R2);
   const F nu = F::sub2(F::zero(), challenge<FID>(u, mont)).norm().canon();
-  SpmvCrossFn<FID> f{ip[0], ix[0], dt[0], ip[1], ix[1], dt[1], ip[2], ix[2], dt[2], dz, (const uint32_t*)e, (uint32_t*)out,
-                     cols <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu, nu, k};
+  SpmvCrossFn<FID> f{m[0].indptr, m[0].indices, m[0].data, m[1].indptr, m[1].indices, m[1].data, m[2].indptr, m[2].indices, m[2].data,
+                     dz, (const uint32_t*)e, (uint32_t*)out, spmv_index_mask(cols), nu, k};
   timed_launch(c, f, rows, &io);
 }
 // The equation half of is_sat / is_sat_relaxed (k_r1cs_sat).  z = [W, u, X] is assembled in the context arena (strict: u = 1 in the
 // vectors' form), W (and E) from HBM or from the host as `flags` says, u and X always from the host.  The 16-byte result record
 // is reset on the stream before the launch and comes back through the context's pinned buffer.  E == nullptr: strict.
 template <int FID>
-static void r1cs_sat_t(Ctx& c, const uint32_t* const* ip, const uint32_t* const* ix, const uint32_t* const* dt, size_t rows, size_t cols,
-                       const void* W, size_t n_w, const void* E, const void* u, const void* X, size_t n_io, uint32_t flags, uint64_t* bad_rows,
-                       uint64_t* first_bad_row) {
+static void r1cs_sat_t(Ctx& c, const CsrView (&m)[3], const void* W, size_t n_w, const void* E, const void* u, const void* X, size_t n_io,
+                       uint32_t flags, uint64_t* bad_rows, uint64_t* first_bad_row) {
   using F = Fp<FID>;
+  const size_t rows = m[0].rows, cols = m[0].cols;
   const bool mont = flags & NMX_SCALARS_MONT, dev = flags & NMX_SCALARS_DEVICE, relaxed = E != nullptr;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // u as the kernel takes it, (p - u) * 2^261 (CrossTermFn), and as z holds it: the caller's word, or ONE in the vectors' form
   uint32_t uw[8] = {1, 0, 0, 0, 0, 0, 0, 0};
   F nu = F::zero();
@@ -1286,7 +1280,7 @@ static void r1cs_sat_t(Ctx& c, const uint32_t* const* ip, const uint32_t* const*
   }
   const F k = mont ? F::from_limbs(FpParams<FID>::C266) : F::from_limbs(FpParams<FID>::R2);
   const bool stage_e = relaxed && !dev;
-  arena_reserve(c, 256 + pad(cols * 32) + (stage_e ? pad(rows * 32) : 0) + 256);
+  arena_reserve(c, 256 + pad256(cols * 32) + (stage_e ? pad256(rows * 32) : 0) + 256);
   if (!c.pinned) HIPCHK(hipHostMalloc((void**)&c.pinned, DeviceBackend::kPinnedBytes, hipHostMallocDefault));
   unsigned long long* rec = (unsigned long long*)c.arena;
   char* dz = c.arena + 256;
@@ -1305,14 +1299,14 @@ static void r1cs_sat_t(Ctx& c, const uint32_t* const* ip, const uint32_t* const*
     HIPCHK(hipMemcpyAsync(dz + n_w * 32, c.pinned + 128, 32, hipMemcpyHostToDevice, c.stream));
     if (n_io) HIPCHK(hipMemcpyAsync(dz + (n_w + 1) * 32, X, n_io * 32, hipMemcpyHostToDevice, c.stream));
     if (stage_e) {
-      char* d = dz + pad(cols * 32);
+      char* d = dz + pad256(cols * 32);
       HIPCHK(hipMemcpyAsync(d, E, rows * 32, hipMemcpyHostToDevice, c.stream));
       de = (const uint32_t*)d;
     }
     be.mark("kernel");
     if (rows) {
-      const R1csSatArgs a{ip[0], ix[0], dt[0], ip[1], ix[1], dt[1], ip[2], ix[2], dt[2], (const uint32_t*)dz, de, rec, (uint32_t)rows,
-                          cols <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu};
+      const R1csSatArgs a{m[0].indptr, m[0].indices, m[0].data, m[1].indptr, m[1].indices, m[1].data, m[2].indptr, m[2].indices, m[2].data,
+                          (const uint32_t*)dz, de, rec, (uint32_t)rows, spmv_index_mask(cols)};
       const dim3 grid((uint32_t)((rows + 255) / 256)), block(256);  // one row per lane, as k_launch<SpmvCrossFn>: the same latency-bound gather
       if (relaxed) hipLaunchKernelGGL((k_r1cs_sat<FID, true>), grid, block, 0, c.stream, a, nu, k);
       else hipLaunchKernelGGL((k_r1cs_sat<FID, false>), grid, block, 0, c.stream, a, nu, k);
@@ -1347,19 +1341,18 @@ template <int FID> static bool batch_invert_t(Ctx& c, const void* v, size_t n, u
   using F = Fp<FID>;
   using H = HostFp4<FID>;
   const bool mont = flags & NMX_SCALARS_MONT, dev = flags & NMX_SCALARS_DEVICE;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // level sizes: n, ceil(n / K(n)), ... down to at most kBinvHostBelow
   std::vector<size_t> sz{n};
   while (sz.back() > kBinvHostBelow) sz.push_back((sz.back() + binv_chunk(sz.back()) - 1) / binv_chunk(sz.back()));
   const size_t L = sz.size() - 1;  // device levels 0 .. L - 1; level L on the host
   size_t need = 256;
-  if (!dev) need += 2 * pad(n * 32);
-  for (size_t l = 1; l <= L; l++) need += 2 * pad(sz[l] * 32);  // products (= the level's input) and prefix / inverse arrays
+  if (!dev) need += 2 * pad256(n * 32);
+  for (size_t l = 1; l <= L; l++) need += 2 * pad256(sz[l] * 32);  // products (= the level's input) and prefix / inverse arrays
   arena_reserve(c, need);
   size_t used = 0;
   auto take = [&](size_t bytes) {
     char* d = c.arena + used;
-    used += pad(bytes);
+    used += pad256(bytes);
     return (uint32_t*)d;
   };
   std::vector<const uint32_t*> in(L + 1);
@@ -1426,17 +1419,16 @@ static void lincomb_t(Ctx& c, const void* const* vecs, const size_t* lens, size_
                       uint32_t flags, void* out) {
   using F = Fp<FID>;
   const bool mont = flags & NMX_SCALARS_MONT, dev = flags & NMX_SCALARS_DEVICE;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  size_t need = pad(k * 8) * 2 + pad(k * 32) + 256;
+  size_t need = pad256(k * 8) * 2 + pad256(k * 32) + 256;
   if (!dev) {
-    for (size_t j = 0; j < k; j++) need += pad(lens[j] * 32);
-    need += pad(n_out * 32);
+    for (size_t j = 0; j < k; j++) need += pad256(lens[j] * 32);
+    need += pad256(n_out * 32);
   }
   arena_reserve(c, need);
   size_t used = 0;
   auto take = [&](size_t bytes) {
     char* d = c.arena + used;
-    used += pad(bytes);
+    used += pad256(bytes);
     return d;
   };
   std::vector<uint64_t> addr(k), ln(k);
@@ -1484,24 +1476,23 @@ static constexpr size_t kHornerTopMin = 1u << 15;  // shorter inputs are launch-
 struct HornerArena {
   char* base;
   size_t used = 0;
-  static size_t pad(size_t b) { return (b + 255) & ~(size_t)255; }
   static size_t need(size_t n, bool top) {
     size_t total = 0;
     while (top && n >= kHornerTopMin) {  // heads + carries of every register-resident level (sized for the smaller chunk)
       const size_t nc = (n + 3) / 4;
-      total += 2 * pad(nc * 32);
+      total += 2 * pad256(nc * 32);
       n = nc;
     }
     for (size_t m = n; m > 1;) {
       const size_t nc = (m + kHornerChunk - 1) / kHornerChunk;
-      total += 2 * pad(nc * 32) + pad((kHornerChunk + 1) * 32);
+      total += 2 * pad256(nc * 32) + pad256((kHornerChunk + 1) * 32);
       m = nc;
     }
-    return total + pad(32) + 256;
+    return total + pad256(32) + 256;
   }
   void* take(size_t bytes) {
     void* p = base + used;
-    used += pad(bytes);
+    used += pad256(bytes);
     return p;
   }
 };
@@ -1547,8 +1538,8 @@ template <int FID> static bool horner_scan_t(Ctx& c, const void* f, size_t n, co
   const F u8 = h8.to_device(), uS = hS.to_device(), uT = hT.to_device(), uG = hG.to_device();
   const F v8 = h8.inv().to_device();  // u != 0 (checked by the caller)
   const size_t nflags = (size_t)nt + 2 * (size_t)ng + 1;  // tile states, group tickets, group states, the start-order counter
-  arena_reserve(c, HornerArena::pad(kScanTblN * 36) + HornerArena::pad(nflags * 4) + HornerArena::pad((size_t)nt * 36) +
-                       2 * HornerArena::pad((size_t)ng * 36) + (dev ? 0 : 2 * HornerArena::pad(n * 32)) + 256);
+  arena_reserve(c, pad256(kScanTblN * 36) + pad256(nflags * 4) + pad256((size_t)nt * 36) +
+                       2 * pad256((size_t)ng * 36) + (dev ? 0 : 2 * pad256(n * 32)) + 256);
   HornerArena ws{c.arena};
   uint32_t* tbl = (uint32_t*)ws.take(kScanTblN * 36);
   uint32_t* flags = (uint32_t*)ws.take(nflags * 4);
@@ -1637,7 +1628,7 @@ static void horner_t(Ctx& c, const void* f, size_t n, const void* u, uint32_t fl
       if (m <= kHornerChunk) break;
     }
   }
-  arena_reserve(c, HornerArena::need(n, G.horner_top != 1) + HornerArena::pad(pwh.size() * 4) + (dev ? 0 : 2 * HornerArena::pad(n * 32)));
+  arena_reserve(c, HornerArena::need(n, G.horner_top != 1) + pad256(pwh.size() * 4) + (dev ? 0 : 2 * pad256(n * 32)));
   HornerArena ws{c.arena};
   uint32_t* d_pw = (uint32_t*)ws.take(pwh.size() * 4);
   HIPCHK(hipMemcpyAsync(d_pw, pwh.data(), pwh.size() * 4, hipMemcpyHostToDevice, c.stream));  // pwh lives to the sync below
@@ -1694,74 +1685,29 @@ static void horner_t(Ctx& c, const void* f, size_t n, const void* u, uint32_t fl
   }
 }
 void fv_suffix_horner(Ctx& c, int field, const void* f, size_t n, const void* u, uint32_t flags, void* out) {
-  switch (field) {
-    case 0: horner_t<0>(c, f, n, u, flags, out); break;
-    case 1: horner_t<1>(c, f, n, u, flags, out); break;
-    case 2: horner_t<2>(c, f, n, u, flags, out); break;
-    case 3: horner_t<3>(c, f, n, u, flags, out); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { horner_t<F()>(c, f, n, u, flags, out); });
 }
 
 void fv_eq_evals(Ctx& c, int field, const void* r_host, uint32_t ell, uint32_t flags, uint32_t* d_out) {
-  switch (field) {
-    case 0: eq_evals_t<0>(c, r_host, ell, flags, d_out); break;
-    case 1: eq_evals_t<1>(c, r_host, ell, flags, d_out); break;
-    case 2: eq_evals_t<2>(c, r_host, ell, flags, d_out); break;
-    case 3: eq_evals_t<3>(c, r_host, ell, flags, d_out); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { eq_evals_t<F()>(c, r_host, ell, flags, d_out); });
 }
 void fv_eq_evals_pair(Ctx& c, int field, const void* r_host, uint32_t ellL, uint32_t ellR, uint32_t flags, uint32_t* d_outL,
                       uint32_t* d_outR) {
-  switch (field) {
-    case 0: eq_evals_pair_t<0>(c, r_host, ellL, ellR, flags, d_outL, d_outR); break;
-    case 1: eq_evals_pair_t<1>(c, r_host, ellL, ellR, flags, d_outL, d_outR); break;
-    case 2: eq_evals_pair_t<2>(c, r_host, ellL, ellR, flags, d_outL, d_outR); break;
-    case 3: eq_evals_pair_t<3>(c, r_host, ellL, ellR, flags, d_outL, d_outR); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { eq_evals_pair_t<F()>(c, r_host, ellL, ellR, flags, d_outL, d_outR); });
 }
 void fv_spmv_convert(Ctx& c, int field, uint32_t* d_data, size_t nnz, uint32_t flags) {
-  switch (field) {
-    case 0: spmv_convert_t<0>(c, d_data, nnz, flags); break;
-    case 1: spmv_convert_t<1>(c, d_data, nnz, flags); break;
-    case 2: spmv_convert_t<2>(c, d_data, nnz, flags); break;
-    case 3: spmv_convert_t<3>(c, d_data, nnz, flags); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { spmv_convert_t<F()>(c, d_data, nnz, flags); });
 }
 void fv_spmv_classify(Ctx& c, int field, const uint32_t* d_data, uint32_t* d_indices, size_t nnz, size_t cols) {
-  if (cols > ((size_t)1 << kSpmvColBits)) return;  // no room for the class bits: every entry stays general
-  switch (field) {
-    case 0: spmv_classify_t<0>(c, d_data, d_indices, nnz); break;
-    case 1: spmv_classify_t<1>(c, d_data, d_indices, nnz); break;
-    case 2: spmv_classify_t<2>(c, d_data, d_indices, nnz); break;
-    case 3: spmv_classify_t<3>(c, d_data, d_indices, nnz); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  if (!~spmv_index_mask(cols)) return;  // no room for the class bits: every entry stays general
+  with_field(field, [&](auto F) { spmv_classify_t<F()>(c, d_data, d_indices, nnz); });
 }
-void fv_spmv_apply(Ctx& c, int field, const uint32_t* indptr, const uint32_t* indices, const uint32_t* data, size_t rows,
-                   size_t cols, const void* z, uint32_t flags, void* out) {
-  switch (field) {
-    case 0: spmv_apply_t<0>(c, indptr, indices, data, rows, cols, z, flags, out); break;
-    case 1: spmv_apply_t<1>(c, indptr, indices, data, rows, cols, z, flags, out); break;
-    case 2: spmv_apply_t<2>(c, indptr, indices, data, rows, cols, z, flags, out); break;
-    case 3: spmv_apply_t<3>(c, indptr, indices, data, rows, cols, z, flags, out); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+void fv_spmv_apply(Ctx& c, int field, const CsrView& m, const void* z, uint32_t flags, void* out) {
+  with_field(field, [&](auto F) { spmv_apply_t<F()>(c, m, z, flags, out); });
 }
 
-void fv_spmv_apply_transposed(Ctx& c, int field, const uint32_t* vptr, const uint32_t* indices, const uint32_t* data, const uint32_t* vout,
-                              const uint32_t* hrow, const uint32_t* hstart, size_t nvirt, size_t nheavy, size_t nparts, size_t rows, size_t cols,
-                              const void* x, uint32_t flags, void* out) {
-  switch (field) {
-    case 0: spmv_apply_transposed_t<0>(c, vptr, indices, data, vout, hrow, hstart, nvirt, nheavy, nparts, rows, cols, x, flags, out); break;
-    case 1: spmv_apply_transposed_t<1>(c, vptr, indices, data, vout, hrow, hstart, nvirt, nheavy, nparts, rows, cols, x, flags, out); break;
-    case 2: spmv_apply_transposed_t<2>(c, vptr, indices, data, vout, hrow, hstart, nvirt, nheavy, nparts, rows, cols, x, flags, out); break;
-    case 3: spmv_apply_transposed_t<3>(c, vptr, indices, data, vout, hrow, hstart, nvirt, nheavy, nparts, rows, cols, x, flags, out); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+void fv_spmv_apply_transposed(Ctx& c, int field, const CsrTransposedView& t, const void* x, uint32_t flags, void* out) {
+  with_field(field, [&](auto F) { spmv_apply_transposed_t<F()>(c, t, x, flags, out); });
 }
 
 // R1CSShape::multiply_vec (src/r1cs/mod.rs:407-471: A z, B z, C z side by side under rayon::join) and compute_eval_table_sparse
@@ -1772,13 +1718,12 @@ void fv_spmv_apply_transposed(Ctx& c, int field, const uint32_t* vptr, const uin
 // the call is stream-ordered like any other (NMX_ASYNC allowed).
 template <int FID> static void spmv_many_t(Ctx& c, const SpmvManyItem* it, size_t k, bool transposed, const void* x, uint32_t flags) {
   const bool async = (flags & NMX_ASYNC) != 0;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   size_t need = 256;
   std::vector<size_t> off(k, 0);
   if (transposed)
     for (size_t i = 0; i < k; i++) {
       off[i] = need;
-      need += pad((it[i].nparts ? it[i].nparts : 1) * 32);
+      need += pad256((it[i].tr.nparts ? it[i].tr.nparts : 1) * 32);
     }
   arena_reserve(c, need);
   require(k >= 1 && k - 1 <= (size_t)Ctx::kSideStreams, NMX_E_ARG, "too many matrices in one call");
@@ -1793,16 +1738,16 @@ template <int FID> static void spmv_many_t(Ctx& c, const SpmvManyItem* it, size_
         st = c.side[i - 1];
         HIPCHK(hipStreamWaitEvent(st, c.side_ev, 0));
       }
-      const SpmvManyItem& m = it[i];
+      uint32_t* out = (uint32_t*)it[i].out;
       if (transposed) {
+        const CsrTransposedView& t = it[i].tr;
         uint32_t* partial = (uint32_t*)(c.arena + off[i]);
-        SpmvSegFn<FID> f{m.vptr, m.tix, m.tdata, (const uint32_t*)x, m.vout, (uint32_t*)m.out, partial,
-                         m.rows <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu};
-        if (m.nvirt) hipLaunchKernelGGL((k_launch<SpmvSegFn<FID>>), dim3((uint32_t)((m.nvirt + 255) / 256)), dim3(256), 0, st, f, (uint32_t)m.nvirt);
-        if (m.nheavy) hipLaunchKernelGGL((k_spmv_heavy<FID>), dim3((uint32_t)m.nheavy), dim3(256), 0, st, m.hrow, m.hstart, (const uint32_t*)partial, (uint32_t*)m.out);
+        SpmvSegFn<FID> f{t.vptr, t.indices, t.data, (const uint32_t*)x, t.vout, out, partial, spmv_index_mask(t.rows)};
+        if (t.nvirt) hipLaunchKernelGGL((k_launch<SpmvSegFn<FID>>), dim3((uint32_t)((t.nvirt + 255) / 256)), dim3(256), 0, st, f, (uint32_t)t.nvirt);
+        if (t.nheavy) hipLaunchKernelGGL((k_spmv_heavy<FID>), dim3((uint32_t)t.nheavy), dim3(256), 0, st, t.hrow, t.hstart, (const uint32_t*)partial, out);
       } else {
-        SpmvFn<FID> f{m.indptr, m.indices, m.data, (const uint32_t*)x, (uint32_t*)m.out,
-                      m.cols <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu};
+        const CsrView& m = it[i].fwd;
+        SpmvFn<FID> f{m.indptr, m.indices, m.data, (const uint32_t*)x, out, spmv_index_mask(m.cols)};
         if (m.rows) hipLaunchKernelGGL((k_launch<SpmvFn<FID>>), dim3((uint32_t)((m.rows + 255) / 256)), dim3(256), 0, st, f, (uint32_t)m.rows);
       }
       HIPCHK(hipGetLastError());
@@ -1829,102 +1774,49 @@ template <int FID> static void spmv_many_t(Ctx& c, const SpmvManyItem* it, size_
   stream_wait(c.stream);
 }
 void fv_spmv_many(Ctx& c, int field, const SpmvManyItem* items, size_t k, bool transposed, const void* x, uint32_t flags) {
-  switch (field) {
-    case 0: spmv_many_t<0>(c, items, k, transposed, x, flags); break;
-    case 1: spmv_many_t<1>(c, items, k, transposed, x, flags); break;
-    case 2: spmv_many_t<2>(c, items, k, transposed, x, flags); break;
-    case 3: spmv_many_t<3>(c, items, k, transposed, x, flags); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { spmv_many_t<F()>(c, items, k, transposed, x, flags); });
 }
 
-void fv_spmv_apply_pair(Ctx& c, int field, const uint32_t* indptr, const uint32_t* indices, const uint32_t* data,
-                        size_t rows, size_t cols, const void* z1, const void* z2, uint32_t flags, void* out1, void* out2) {
-  switch (field) {
-    case 0: spmv_apply_pair_t<0>(c, indptr, indices, data, rows, cols, z1, z2, flags, out1, out2); break;
-    case 1: spmv_apply_pair_t<1>(c, indptr, indices, data, rows, cols, z1, z2, flags, out1, out2); break;
-    case 2: spmv_apply_pair_t<2>(c, indptr, indices, data, rows, cols, z1, z2, flags, out1, out2); break;
-    case 3: spmv_apply_pair_t<3>(c, indptr, indices, data, rows, cols, z1, z2, flags, out1, out2); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+void fv_spmv_apply_pair(Ctx& c, int field, const CsrView& m, const void* z1, const void* z2, uint32_t flags, void* out1, void* out2) {
+  with_field(field, [&](auto F) { spmv_apply_pair_t<F()>(c, m, z1, z2, flags, out1, out2); });
 }
-void fv_r1cs_cross_term(Ctx& c, int field, const uint32_t* const* ip, const uint32_t* const* ix, const uint32_t* const* dt, size_t rows,
-                        size_t cols, const void* z1, const void* z2, const void* e, const void* u, uint32_t flags, void* out) {
-  switch (field) {
-    case 0: r1cs_cross_term_t<0>(c, ip, ix, dt, rows, cols, z1, z2, e, u, flags, out); break;
-    case 1: r1cs_cross_term_t<1>(c, ip, ix, dt, rows, cols, z1, z2, e, u, flags, out); break;
-    case 2: r1cs_cross_term_t<2>(c, ip, ix, dt, rows, cols, z1, z2, e, u, flags, out); break;
-    case 3: r1cs_cross_term_t<3>(c, ip, ix, dt, rows, cols, z1, z2, e, u, flags, out); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+void fv_r1cs_cross_term(Ctx& c, int field, const CsrView (&abc)[3], const void* z1, const void* z2, const void* e, const void* u,
+                        uint32_t flags, void* out) {
+  with_field(field, [&](auto F) { r1cs_cross_term_t<F()>(c, abc, z1, z2, e, u, flags, out); });
 }
-void fv_r1cs_sat(Ctx& c, int field, const uint32_t* const* ip, const uint32_t* const* ix, const uint32_t* const* dt, size_t rows, size_t cols,
-                 const void* W, size_t n_w, const void* E, const void* u, const void* X, size_t n_io, uint32_t flags, uint64_t* bad_rows,
-                 uint64_t* first_bad_row) {
-  switch (field) {
-    case 0: r1cs_sat_t<0>(c, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); break;
-    case 1: r1cs_sat_t<1>(c, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); break;
-    case 2: r1cs_sat_t<2>(c, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); break;
-    case 3: r1cs_sat_t<3>(c, ip, ix, dt, rows, cols, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+void fv_r1cs_sat(Ctx& c, int field, const CsrView (&abc)[3], const void* W, size_t n_w, const void* E, const void* u, const void* X,
+                 size_t n_io, uint32_t flags, uint64_t* bad_rows, uint64_t* first_bad_row) {
+  with_field(field, [&](auto F) { r1cs_sat_t<F()>(c, abc, W, n_w, E, u, X, n_io, flags, bad_rows, first_bad_row); });
 }
 void fv_nifs_fold(Ctx& c, int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e,
                   const void* r, uint32_t flags, void* w, void* e) {
-  switch (field) {
-    case 0: nifs_fold_t<0>(c, w1, w2, n_w, e1, t, n_e, r, flags, w, e); break;
-    case 1: nifs_fold_t<1>(c, w1, w2, n_w, e1, t, n_e, r, flags, w, e); break;
-    case 2: nifs_fold_t<2>(c, w1, w2, n_w, e1, t, n_e, r, flags, w, e); break;
-    case 3: nifs_fold_t<3>(c, w1, w2, n_w, e1, t, n_e, r, flags, w, e); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { nifs_fold_t<F()>(c, w1, w2, n_w, e1, t, n_e, r, flags, w, e); });
 }
 bool fv_batch_invert(Ctx& c, int field, const void* v, size_t n, uint32_t flags, void* out) {
-  switch (field) {
-    case 0: return batch_invert_t<0>(c, v, n, flags, out);
-    case 1: return batch_invert_t<1>(c, v, n, flags, out);
-    case 2: return batch_invert_t<2>(c, v, n, flags, out);
-    case 3: return batch_invert_t<3>(c, v, n, flags, out);
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  return with_field(field, [&](auto F) { return batch_invert_t<F()>(c, v, n, flags, out); });
 }
 void fv_lincomb(Ctx& c, int field, const void* const* vecs, const size_t* lens, size_t k, const void* s, size_t n_out,
                 uint32_t flags, void* out) {
-  switch (field) {
-    case 0: lincomb_t<0>(c, vecs, lens, k, s, n_out, flags, out); break;
-    case 1: lincomb_t<1>(c, vecs, lens, k, s, n_out, flags, out); break;
-    case 2: lincomb_t<2>(c, vecs, lens, k, s, n_out, flags, out); break;
-    case 3: lincomb_t<3>(c, vecs, lens, k, s, n_out, flags, out); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { lincomb_t<F()>(c, vecs, lens, k, s, n_out, flags, out); });
 }
 
-#define FIELD_SWITCH(field, CALL)                                        \
-  switch (field) {                                                       \
-    case 0: FieldImpl<0>::CALL; break;                                   \
-    case 1: FieldImpl<1>::CALL; break;                                   \
-    case 2: FieldImpl<2>::CALL; break;                                   \
-    case 3: FieldImpl<3>::CALL; break;                                   \
-    default: throw Fail{NMX_E_ARG, "bad field id"};                      \
-  }
-
 void fv_axpy(Ctx& c, int field, const void* a, const void* b, const void* r, size_t n, uint32_t flags, void* out) {
-  FIELD_SWITCH(field, axpy(c, a, b, r, n, flags, out));
+  with_field(field, [&](auto F) { FieldImpl<F()>::axpy(c, a, b, r, n, flags, out); });
 }
 void fv_axpy2(Ctx& c, int field, const void* a, const void* b, const void* cc, const void* r, size_t n, uint32_t flags,
               void* out) {
-  FIELD_SWITCH(field, axpy2(c, a, b, cc, r, n, flags, out));
+  with_field(field, [&](auto F) { FieldImpl<F()>::axpy2(c, a, b, cc, r, n, flags, out); });
 }
 void fv_cross_term(Ctx& c, int field, const void* az, const void* bz, const void* cz, const void* e, const void* u,
                    size_t n, uint32_t flags, void* out) {
-  FIELD_SWITCH(field, cross_term(c, az, bz, cz, e, u, n, flags, out));
+  with_field(field, [&](auto F) { FieldImpl<F()>::cross_term(c, az, bz, cz, e, u, n, flags, out); });
 }
 void fv_cross_term2(Ctx& c, int field, const void* az, const void* bz, const void* cz, const void* e1, const void* e2,
                     const void* u, size_t n, uint32_t flags, void* out) {
-  FIELD_SWITCH(field, cross_term2(c, az, bz, cz, e1, e2, u, n, flags, out));
+  with_field(field, [&](auto F) { FieldImpl<F()>::cross_term2(c, az, bz, cz, e1, e2, u, n, flags, out); });
 }
 void fv_vec_add(Ctx& c, int field, const void* a, const void* b, size_t n, uint32_t flags, void* out) {
-  FIELD_SWITCH(field, vec_add(c, a, b, n, flags, out));
+  with_field(field, [&](auto F) { FieldImpl<F()>::vec_add(c, a, b, n, flags, out); });
 }
 // ---- HyperKZG's fold loop as one call (round 6) ---------------------------------------------------------------------------
 // `for i in 0..ell-1 { Pi[j] = x[ell-i-1] * (P[2j+1] - P[2j]) + P[2j] }` (src/provider/hyperkzg.rs:1085-1095): ell - 1 folds, each
@@ -2006,18 +1898,12 @@ static void fold_chain_t(Ctx& c, const void* p, size_t len, const void* xs, size
   stream_wait(c.stream);
 }
 void fv_fold_chain(Ctx& c, int field, const void* p, size_t len, const void* xs, size_t k, uint32_t flags, void* const* outs) {
-  switch (field) {
-    case 0: fold_chain_t<0>(c, p, len, xs, k, flags, outs); break;
-    case 1: fold_chain_t<1>(c, p, len, xs, k, flags, outs); break;
-    case 2: fold_chain_t<2>(c, p, len, xs, k, flags, outs); break;
-    case 3: fold_chain_t<3>(c, p, len, xs, k, flags, outs); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { fold_chain_t<F()>(c, p, len, xs, k, flags, outs); });
 }
 
 void fv_bind(Ctx& c, int field, const void* z, size_t z_len, size_t lo_off, size_t hi_off, size_t stride,
              const void* r, size_t n_out, uint32_t flags, void* out) {
-  FIELD_SWITCH(field, bind(c, z, z_len, lo_off, hi_off, stride, r, n_out, flags, out));
+  with_field(field, [&](auto F) { FieldImpl<F()>::bind(c, z, z_len, lo_off, hi_off, stride, r, n_out, flags, out); });
 }
 
 }  // namespace nmx

@@ -163,44 +163,22 @@ template <int FID> static bool ipa_invert_t(const void* r, uint32_t flags, void*
   return true;
 }
 
-#define NMX_IPA_FIELD_SWITCH(CALL)                      \
-  switch (field) {                                      \
-    case 0: CALL(0); break;                             \
-    case 1: CALL(1); break;                             \
-    case 2: CALL(2); break;                             \
-    case 3: CALL(3); break;                             \
-    default: throw Fail{NMX_E_ARG, "bad field id"};     \
-  }
-
 void fv_ipa_round(Ctx& c, int field, const uint32_t* a, const uint32_t* b, const uint32_t* S, uint32_t* a_out, uint32_t* b_out, uint32_t* S_out,
                   size_t n, size_t len, const void* r_prev, const void* rinv_prev, uint32_t flags, uint32_t* vL, uint32_t* vR, hipEvent_t done,
                   const uint32_t** partial_host) {
-#define X(FID) ipa_round_t<FID>(c, a, b, S, a_out, b_out, S_out, n, len, r_prev, rinv_prev, flags, vL, vR, done, partial_host)
-  NMX_IPA_FIELD_SWITCH(X)
-#undef X
+  with_field(field, [&](auto F) { ipa_round_t<F()>(c, a, b, S, a_out, b_out, S_out, n, len, r_prev, rinv_prev, flags, vL, vR, done, partial_host); });
 }
 void fv_ipa_scalar(int field, const uint32_t* partial_host, size_t n, int which, uint32_t flags, uint8_t* out32) {
-#define X(FID) ipa_scalar_t<FID>(partial_host, n, which, flags, out32)
-  NMX_IPA_FIELD_SWITCH(X)
-#undef X
+  with_field(field, [&](auto F) { ipa_scalar_t<F()>(partial_host, n, which, flags, out32); });
 }
 void fv_ipa_last(Ctx& c, int field, const uint32_t* a, const void* r, const void* rinv, uint32_t flags, uint32_t* dout, uint8_t* out32) {
-#define X(FID) ipa_last_t<FID>(c, a, r, rinv, flags, dout, out32)
-  NMX_IPA_FIELD_SWITCH(X)
-#undef X
+  with_field(field, [&](auto F) { ipa_last_t<F()>(c, a, r, rinv, flags, dout, out32); });
 }
 void fv_ipa_one(Ctx& c, int field, uint32_t* S) {
-#define X(FID) ipa_one_t<FID>(c, S)
-  NMX_IPA_FIELD_SWITCH(X)
-#undef X
+  with_field(field, [&](auto F) { ipa_one_t<F()>(c, S); });
 }
 bool fv_ipa_invert(int field, const void* r, uint32_t flags, void* out) {
-  bool ok = false;
-#define X(FID) ok = ipa_invert_t<FID>(r, flags, out)
-  NMX_IPA_FIELD_SWITCH(X)
-#undef X
-  return ok;
+  return with_field(field, [&](auto F) { return ipa_invert_t<F()>(r, flags, out); });
 }
-#undef NMX_IPA_FIELD_SWITCH
 
 }  // namespace nmx

@@ -223,32 +223,17 @@ template <int FID> static void ipa_verify_mul_t(const void* a, const void* b, ui
   V::store(V::load(a, mont, "scalar >= field modulus") * V::load(b, mont, "scalar >= field modulus"), mont, out32);
 }
 
-#define NMX_IPAV_FIELD_SWITCH(CALL)                     \
-  switch (field) {                                      \
-    case 0: CALL(0); break;                             \
-    case 1: CALL(1); break;                             \
-    case 2: CALL(2); break;                             \
-    case 3: CALL(3); break;                             \
-    default: throw Fail{NMX_E_ARG, "bad field id"};     \
-  }
 void fv_ipa_verify_s(Ctx& c, int field, const void* rs, uint32_t ell, const void* point, uint32_t flags, uint64_t lo, uint64_t cnt,
                      uint32_t* s_out, const uint32_t* b_dev, uint8_t* rsq_abi, uint8_t* rinvsq_abi, uint8_t* bhat_point,
                      const uint32_t** partial_host, uint32_t* blocks) {
-#define X(FID) ipa_verify_s_t<FID>(c, rs, ell, point, flags, lo, cnt, s_out, b_dev, rsq_abi, rinvsq_abi, bhat_point, partial_host, blocks)
-  NMX_IPAV_FIELD_SWITCH(X)
-#undef X
+  with_field(field, [&](auto F) { ipa_verify_s_t<F()>(c, rs, ell, point, flags, lo, cnt, s_out, b_dev, rsq_abi, rinvsq_abi, bhat_point, partial_host, blocks); });
 }
 void fv_ipa_verify_bhat(int field, const uint32_t* partial_host, uint32_t blocks, uint32_t flags, uint8_t* out32) {
-#define X(FID) ipa_verify_bhat_t<FID>(partial_host, blocks, flags, out32)
-  NMX_IPAV_FIELD_SWITCH(X)
-#undef X
+  with_field(field, [&](auto F) { ipa_verify_bhat_t<F()>(partial_host, blocks, flags, out32); });
 }
 void fv_field_mul_host(int field, const void* a, const void* b, uint32_t flags, uint8_t* out32) {
-#define X(FID) ipa_verify_mul_t<FID>(a, b, flags, out32)
-  NMX_IPAV_FIELD_SWITCH(X)
-#undef X
+  with_field(field, [&](auto F) { ipa_verify_mul_t<F()>(a, b, flags, out32); });
 }
-#undef NMX_IPAV_FIELD_SWITCH
 #endif
 
 }  // namespace nmx

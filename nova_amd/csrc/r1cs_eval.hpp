@@ -135,7 +135,7 @@ static inline uint32_t r1cs_eval_bits(size_t n) {
 }
 
 template <int FID>
-static void r1cs_eval_t(Ctx& c, const R1csEvalItem* it, size_t k, const void* r_x, uint32_t ell_x, const void* r_y, uint32_t ell_y,
+static void r1cs_eval_t(Ctx& c, const CsrView* it, size_t k, const void* r_x, uint32_t ell_x, const void* r_y, uint32_t ell_y,
                         uint32_t flags, uint8_t* out) {
   using F = Fp<FID>;
   const bool mont = flags & NMX_SCALARS_MONT;
@@ -163,11 +163,10 @@ static void r1cs_eval_t(Ctx& c, const R1csEvalItem* it, size_t k, const void* r_
   }
   const uint32_t sx = effx / 2, lx = effx - sx;
   const uint32_t bpm = r1cs_eval_blocks(max_rows);
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   // arena: [0, kScratch) is what eq_evals_t stages its own sqrt-size tables in (its arena_reserve is then a no-op and moves nothing)
   constexpr size_t kScratch = 2 * ((size_t)32 << kMax) + 512;
-  const size_t oXL = kScratch, oXR = oXL + pad((size_t)32 << lx), oTY = oXR + pad((size_t)32 << sx), oP = oTY + pad((size_t)32 << effy),
-               oOut = oP + pad((size_t)32 * k * bpm), total = oOut + 256;
+  const size_t oXL = kScratch, oXR = oXL + pad256((size_t)32 << lx), oTY = oXR + pad256((size_t)32 << sx), oP = oTY + pad256((size_t)32 << effy),
+               oOut = oP + pad256((size_t)32 * k * bpm), total = oOut + 256;
   arena_reserve(c, total);
   if (!c.pinned) HIPCHK(hipHostMalloc((void**)&c.pinned, DeviceBackend::kPinnedBytes, hipHostMallocDefault));
   const bool prof = G.profiling;
@@ -185,7 +184,7 @@ static void r1cs_eval_t(Ctx& c, const R1csEvalItem* it, size_t k, const void* r_
     for (size_t j = 0; j < k; j++) {
       a.indptr[j] = it[j].indptr, a.indices[j] = it[j].indices, a.data[j] = it[j].data;
       a.rows[j] = (uint32_t)it[j].rows;
-      a.colmask[j] = it[j].cols <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu;
+      a.colmask[j] = spmv_index_mask(it[j].cols);
     }
     a.xL = f.outL, a.xR = f.outR, a.ty = (const uint32_t*)(c.arena + oTY);
     a.partial = (uint32_t*)(c.arena + oP), a.sx = sx, a.bpm = bpm;
@@ -209,15 +208,9 @@ static void r1cs_eval_t(Ctx& c, const R1csEvalItem* it, size_t k, const void* r_
   }
 }
 
-void fv_r1cs_evaluate(Ctx& c, int field, const R1csEvalItem* items, size_t k, const void* r_x, uint32_t ell_x, const void* r_y,
+void fv_r1cs_evaluate(Ctx& c, int field, const CsrView* mats, size_t k, const void* r_x, uint32_t ell_x, const void* r_y,
                       uint32_t ell_y, uint32_t flags, uint8_t* out) {
-  switch (field) {
-    case 0: r1cs_eval_t<0>(c, items, k, r_x, ell_x, r_y, ell_y, flags, out); break;
-    case 1: r1cs_eval_t<1>(c, items, k, r_x, ell_x, r_y, ell_y, flags, out); break;
-    case 2: r1cs_eval_t<2>(c, items, k, r_x, ell_x, r_y, ell_y, flags, out); break;
-    case 3: r1cs_eval_t<3>(c, items, k, r_x, ell_x, r_y, ell_y, flags, out); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { r1cs_eval_t<F()>(c, mats, k, r_x, ell_x, r_y, ell_y, flags, out); });
 }
 #endif
 

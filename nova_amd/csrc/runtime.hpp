@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/nova_mi355x.h"
+#include "field_dispatch.hpp"  // Fail, with_field
 #include "curves.hpp"
 #include "msm_pipeline.hpp"
 #include "curve_quad.hpp"
@@ -30,12 +31,8 @@
 namespace nmx {
 
 // ---------------------------------------------------------------------------------------------------
-// errors
+// errors (struct Fail: field_dispatch.hpp)
 // ---------------------------------------------------------------------------------------------------
-struct Fail {
-  int code;
-  std::string msg;
-};
 #define HIPCHK(x)                                                                                  \
   do {                                                                                             \
     hipError_t e_ = (x);                                                                           \
@@ -45,6 +42,8 @@ struct Fail {
 static inline void require(bool ok, int code, const char* msg) {
   if (!ok) throw Fail{code, msg};
 }
+// workspace carves are 256-byte aligned
+static inline size_t pad256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // ---------------------------------------------------------------------------------------------------
 // generic launch trampoline: one lane per tid
@@ -261,6 +260,16 @@ template <class R> class PoolFuture {
 
 // conversion, no validation (the slice cache adding window tables to a key it holds)
 static constexpr uint32_t NMX_BASES_INTERNAL = 1u << 30;
+// A resident CSR matrix as the field-vector layer takes it (Global::SparseSet::view()), and its transposed form in virtual rows
+// (Global::SparseSet::Transposed::view()): device pointers the registry keeps alive; rows / cols are those of M in both
+struct CsrView {
+  const uint32_t *indptr = nullptr, *indices = nullptr, *data = nullptr;
+  size_t rows = 0, cols = 0;
+};
+struct CsrTransposedView {
+  const uint32_t *vptr = nullptr, *indices = nullptr, *data = nullptr, *vout = nullptr, *hrow = nullptr, *hstart = nullptr;
+  size_t nvirt = 0, nheavy = 0, nparts = 0, rows = 0, cols = 0;
+};
 struct Global {
   std::mutex mu;
   bool inited = false;
@@ -288,6 +297,9 @@ struct Global {
       uint32_t *vptr = nullptr, *indices = nullptr, *data = nullptr, *vout = nullptr, *hrow = nullptr, *hstart = nullptr;
       size_t nvirt = 0, nheavy = 0, nparts = 0;
       int dev = 0;
+      CsrTransposedView view(const SparseSet& of) const {
+        return {vptr, indices, data, vout, hrow, hstart, nvirt, nheavy, nparts, of.rows, of.cols};
+      }
       ~Transposed();  // capi.hip
     };
     std::mutex t_mu;
@@ -295,6 +307,7 @@ struct Global {
     SparseSet() = default;
     SparseSet(const SparseSet&) = delete;
     SparseSet& operator=(const SparseSet&) = delete;
+    CsrView view() const { return {indptr, indices, data, rows, cols}; }
     ~SparseSet();  // capi.hip
   };
   std::unordered_map<uint64_t, std::shared_ptr<SparseSet>> sparse;
@@ -388,7 +401,7 @@ struct DeviceBackend {
   explicit DeviceBackend(Ctx& ctx, bool dry_, bool prof_) : c(ctx), dry(dry_), prof(prof_) {}
 
   template <class T> T* alloc(size_t count) {
-    size_t bytes = (count * sizeof(T) + 255) & ~(size_t)255;
+    size_t bytes = pad256(count * sizeof(T));
     T* p = (T*)(c.arena + used);
     used += bytes;
     if (!dry) require(used <= c.cap, NMX_E_HIP, "workspace arena overflow");
@@ -713,21 +726,16 @@ void fv_bind(Ctx&, int field, const void* z, size_t z_len, size_t lo_off, size_t
              size_t n_out, uint32_t flags, void* out);
 
 void fv_suffix_horner(Ctx&, int field, const void* f, size_t n, const void* u, uint32_t flags, void* out);
-void fv_r1cs_cross_term(Ctx&, int field, const uint32_t* const* indptr, const uint32_t* const* indices, const uint32_t* const* data,
-                        size_t rows, size_t cols, const void* z1, const void* z2, const void* e, const void* u, uint32_t flags, void* out);
+void fv_r1cs_cross_term(Ctx&, int field, const CsrView (&abc)[3], const void* z1, const void* z2, const void* e, const void* u,
+                        uint32_t flags, void* out);  // A, B, C of one shape
 // is_sat / is_sat_relaxed, the equation half (fieldvec.hip k_r1cs_sat): z = [W, u, X]; E == nullptr: strict (u ignored).  W, E follow
 // NMX_SCALARS_DEVICE, u and X are host pointers.  Synchronous: *bad_rows = violated rows, *first_bad_row = the lowest (2^64 - 1: none)
-void fv_r1cs_sat(Ctx&, int field, const uint32_t* const* indptr, const uint32_t* const* indices, const uint32_t* const* data, size_t rows,
-                 size_t cols, const void* W, size_t n_w, const void* E, const void* u, const void* X, size_t n_io, uint32_t flags,
-                 uint64_t* bad_rows, uint64_t* first_bad_row);
+void fv_r1cs_sat(Ctx&, int field, const CsrView (&abc)[3], const void* W, size_t n_w, const void* E, const void* u, const void* X,
+                 size_t n_io, uint32_t flags, uint64_t* bad_rows, uint64_t* first_bad_row);
 // RelaxedR1CSSNARK::verify's multi_evaluate (r1cs_eval.hpp): out[j] = sum over the entries of matrix j of T_x[row] T_y[col] val, k <= 8
 // matrices in one pass; r_x / r_y are host arrays in the ABI form of `flags` (NMX_SCALARS_MONT or canonical), out is a host buffer
 // of k x 32 bytes in the same form.  Synchronous.  rows <= 2^ell_x and cols <= 2^ell_y are the caller's to check.
-struct R1csEvalItem {
-  const uint32_t *indptr = nullptr, *indices = nullptr, *data = nullptr;
-  size_t rows = 0, cols = 0;
-};
-void fv_r1cs_evaluate(Ctx&, int field, const R1csEvalItem* items, size_t k, const void* r_x, uint32_t ell_x, const void* r_y,
+void fv_r1cs_evaluate(Ctx&, int field, const CsrView* mats, size_t k, const void* r_x, uint32_t ell_x, const void* r_y,
                       uint32_t ell_y, uint32_t flags, uint8_t* out);
 void fv_nifs_fold(Ctx&, int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e, const void* r,
                   uint32_t flags, void* w, void* e);
@@ -736,10 +744,8 @@ void fv_eq_evals_pair(Ctx&, int field, const void* r_host, uint32_t ellL, uint32
                       uint32_t* d_outR);  // both tables of an evaluation, one launch when both fit the direct kernel
 void fv_spmv_convert(Ctx&, int field, uint32_t* d_data, size_t nnz, uint32_t flags);
 void fv_spmv_classify(Ctx&, int field, const uint32_t* d_data, uint32_t* d_indices, size_t nnz, size_t cols);
-void fv_spmv_apply(Ctx&, int field, const uint32_t* indptr, const uint32_t* indices, const uint32_t* data, size_t rows,
-                   size_t cols, const void* z, uint32_t flags, void* out);
-void fv_spmv_apply_pair(Ctx&, int field, const uint32_t* indptr, const uint32_t* indices, const uint32_t* data,
-                        size_t rows, size_t cols, const void* z1, const void* z2, uint32_t flags, void* out1, void* out2);
+void fv_spmv_apply(Ctx&, int field, const CsrView& m, const void* z, uint32_t flags, void* out);
+void fv_spmv_apply_pair(Ctx&, int field, const CsrView& m, const void* z1, const void* z2, uint32_t flags, void* out1, void* out2);
 bool fv_batch_invert(Ctx&, int field, const void* v, size_t n, uint32_t flags, void* out);  // false: an element is zero
 void fv_lincomb(Ctx&, int field, const void* const* vecs, const size_t* lens, size_t k, const void* s, size_t n_out,
                 uint32_t flags, void* out);
@@ -769,10 +775,9 @@ void fv_bind_eq_sums(Ctx&, int field, int mode, const void* A, const void* B, co
                      const void* eqL, size_t nL, const void* eqR, size_t nR, uint32_t shift, uint32_t flags, void* oA,
                      void* oB, void* oC, uint8_t* out);  // sumcheck.hip
 void fv_fold_chain(Ctx&, int field, const void* p, size_t len, const void* xs, size_t k, uint32_t flags, void* const* outs);  // fieldvec.hip
-struct SpmvManyItem {  // one matrix of nmx_spmv_apply_many (fieldvec.hip spmv_many_t)
-  const uint32_t *indptr = nullptr, *indices = nullptr, *data = nullptr;                                                  // CSR (forward)
-  const uint32_t *vptr = nullptr, *tix = nullptr, *tdata = nullptr, *vout = nullptr, *hrow = nullptr, *hstart = nullptr;  // M^T in virtual rows
-  size_t nvirt = 0, nheavy = 0, nparts = 0, rows = 0, cols = 0;
+struct SpmvManyItem {  // one matrix of nmx_spmv_apply_many (fieldvec.hip spmv_many_t): the form the call's direction reads, and its output
+  CsrView fwd;
+  CsrTransposedView tr;
   void* out = nullptr;
 };
 void fv_spmv_many(Ctx&, int field, const SpmvManyItem* items, size_t k, bool transposed, const void* x, uint32_t flags);
@@ -780,9 +785,7 @@ void fv_mle_multi_eval(Ctx&, int field, const void* const* zs, size_t k, size_t 
                        uint32_t flags, uint8_t* out);  // sumcheck_prove.hpp: HBM-resident polynomials, results through the mailbox
 void fv_eq_sums(Ctx&, int field, int mode, const void* A, const void* B, const void* C, size_t len, const void* eqL,
                 size_t nL, const void* eqR, size_t nR, uint32_t shift, uint32_t flags, uint8_t* out);  // sumcheck.hip
-void fv_spmv_apply_transposed(Ctx&, int field, const uint32_t* vptr, const uint32_t* indices, const uint32_t* data, const uint32_t* vout,
-                              const uint32_t* hrow, const uint32_t* hstart, size_t nvirt, size_t nheavy, size_t nparts, size_t rows, size_t cols,
-                              const void* x, uint32_t flags, void* out);
+void fv_spmv_apply_transposed(Ctx&, int field, const CsrTransposedView& t, const void* x, uint32_t flags, void* out);
 // Spartan's sum-check provers, one call each (sumcheck_prove.hpp); which = 3: cubic with three inputs, 4: quad_prod
 using TranscriptFn = int (*)(void* ctx, const uint8_t* coeffs, size_t n_coeffs, uint8_t* challenge32);
 void fv_sumcheck_prove(Ctx&, int field, int which, const void* claim, const void* taus, size_t num_rounds, void* A, void* B, void* C,

@@ -16,6 +16,9 @@ template <int FID> NMX_HD void st(uint32_t* p, size_t i, const Fp<FID>& v) { v.c
 // 4 B of matrix traffic instead of 36 B and its 32-byte coefficient is never read -- SpMV is gather-bound, the saving
 // is bytes, not multiplications.  Classes: 0 general, 1 +1, 2 -1, 3..8 +2..+7, 9..14 -2..-7.
 static constexpr uint32_t kSpmvColBits = 28;
+// what of an index word is the index, for a matrix whose gathered dimension has `extent` entries: the class bits are there only
+// when the indices leave them room (otherwise every entry is class 0, general)
+static inline uint32_t spmv_index_mask(size_t extent) { return extent <= ((size_t)1 << kSpmvColBits) ? (1u << kSpmvColBits) - 1u : 0xffffffffu; }
 
 // coefficient class `cls` (>= 1) applied to z: a value < p, canonical.  z is any 256-bit value: it is reduced first (a
 // z >= p -- the general Montgomery path reduces those correctly too -- would otherwise leave k z beyond canon()'s 16 p)

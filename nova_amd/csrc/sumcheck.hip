@@ -325,15 +325,14 @@ static void eq_sums_t(Ctx& c, const void* A, const void* B, const void* C, size_
   const uint32_t blocks = want < 1 ? 1 : (want > cap ? cap : want);
   // staging (host operands) + partials + result
   size_t need = (size_t)blocks * 64 + 64 + 512;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  if (!dev) need += pad(len * 32) * (MODE == 3 ? 3 : MODE == 2 ? 2 : 1) + pad(nL * 32) + pad(nR * 32);
+  if (!dev) need += pad256(len * 32) * (MODE == 3 ? 3 : MODE == 2 ? 2 : 1) + pad256(nL * 32) + pad256(nR * 32);
   arena_reserve(c, need);
   size_t used = 0;
   auto stage = [&](const void* p, size_t elems) -> const uint32_t* {
     if (!p) return nullptr;
     if (dev) return (const uint32_t*)p;
     char* d = c.arena + used;
-    used += pad(elems * 32);
+    used += pad256(elems * 32);
     HIPCHK(hipMemcpyAsync(d, p, elems * 32, hipMemcpyHostToDevice, c.stream));
     return (const uint32_t*)d;
   };
@@ -343,7 +342,7 @@ static void eq_sums_t(Ctx& c, const void* A, const void* B, const void* C, size_
   const uint32_t* dL = stage(eqL, nL);
   const uint32_t* dR = stage(eqR, nR);
   uint32_t* partial = (uint32_t*)(c.arena + used);
-  used += pad((size_t)blocks * 64);
+  used += pad256((size_t)blocks * 64);
   uint32_t* dout = (uint32_t*)(c.arena + used);
   // Form factor Fm = 1 (canonical) or 2^256 (Montgomery); R' = 2^261; a product of two stored elements comes out
   // as x*y * Fm^2 / R'.  MODE 3 brings c0*Fm to that scale with the plain constant Fm; MODE 2 subtracts the
@@ -466,10 +465,9 @@ static void bind_eq_sums_t(Ctx& c, const void* A, const void* B, const void* C, 
   const uint32_t per = hq <= (1u << 20) ? 1u : 4u;
   const uint32_t want = (hq + 256 * per - 1) / (256 * per);
   const uint32_t blocks = want < 1 ? 1 : (want > 4096 ? 4096 : want);
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
-  arena_reserve(c, pad((size_t)blocks * 64) + 64 + 512);
+  arena_reserve(c, pad256((size_t)blocks * 64) + 64 + 512);
   uint32_t* partial = (uint32_t*)c.arena;
-  uint32_t* dout = (uint32_t*)(c.arena + pad((size_t)blocks * 64));
+  uint32_t* dout = (uint32_t*)(c.arena + pad256((size_t)blocks * 64));
   F fconst = F::zero();
   if (MODE == 3) {
     if (mont) fconst = pow2_plain<FID>(256);
@@ -515,21 +513,9 @@ static void bind_eq_sums_t(Ctx& c, const void* A, const void* B, const void* C, 
 void fv_bind_eq_sums(Ctx& c, int field, int mode, const void* A, const void* B, const void* C, size_t len, const void* r,
                      const void* eqL, size_t nL, const void* eqR, size_t nR, uint32_t shift, uint32_t flags, void* oA,
                      void* oB, void* oC, uint8_t* out) {
-#define BES(FID)                                                                                                    \
-  switch (mode) {                                                                                                   \
-    case 1: bind_eq_sums_t<FID, 1>(c, A, B, C, len, r, eqL, nL, eqR, nR, shift, flags, oA, oB, oC, out); return;    \
-    case 2: bind_eq_sums_t<FID, 2>(c, A, B, C, len, r, eqL, nL, eqR, nR, shift, flags, oA, oB, oC, out); return;    \
-    case 3: bind_eq_sums_t<FID, 3>(c, A, B, C, len, r, eqL, nL, eqR, nR, shift, flags, oA, oB, oC, out); return;    \
-    default: throw Fail{NMX_E_ARG, "bad sum-check mode"};                                                           \
-  }
-  switch (field) {
-    case 0: BES(0)
-    case 1: BES(1)
-    case 2: BES(2)
-    case 3: BES(3)
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
-#undef BES
+  with_field(field, [&](auto F) {
+    with_index<1, 3>(mode, "bad sum-check mode", [&](auto M) { bind_eq_sums_t<F(), M()>(c, A, B, C, len, r, eqL, nL, eqR, nR, shift, flags, oA, oB, oC, out); });
+  });
 }
 
 // ---- k polynomials evaluated at m points in one launch ------------------------------------------------------------
@@ -614,7 +600,6 @@ static void eval_multi_t(Ctx& c, const void* const* polys, const size_t* lens, s
                          uint32_t flags, uint8_t* out) {
   using F = Fp<FID>;
   const bool mont = flags & NMX_SCALARS_MONT, dev = flags & NMX_SCALARS_DEVICE;
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   std::vector<EvalPoly> desc(k);
   uint32_t blocks = 0;
   size_t stage_bytes = 0;
@@ -622,16 +607,16 @@ static void eval_multi_t(Ctx& c, const void* const* polys, const size_t* lens, s
     const uint32_t nb = (uint32_t)((lens[i] + 256 * kEvalChunk - 1) / (256 * kEvalChunk));
     desc[i] = EvalPoly{nullptr, (uint32_t)lens[i], blocks, nb ? nb : 1};
     blocks += desc[i].nblocks;
-    if (!dev) stage_bytes += pad(lens[i] * 32);
+    if (!dev) stage_bytes += pad256(lens[i] * 32);
   }
-  const size_t tab_bytes = pad(m * 32) + pad(m * 256 * 32) + pad(m * 20 * 32);
-  const size_t need = stage_bytes + pad(k * sizeof(EvalPoly)) + tab_bytes + pad((size_t)blocks * kEvalMaxPts * 32) +
-                      pad(k * m * 32) + 512;
+  const size_t tab_bytes = pad256(m * 32) + pad256(m * 256 * 32) + pad256(m * 20 * 32);
+  const size_t need = stage_bytes + pad256(k * sizeof(EvalPoly)) + tab_bytes + pad256((size_t)blocks * kEvalMaxPts * 32) +
+                      pad256(k * m * 32) + 512;
   arena_reserve(c, need);
   size_t used = 0;
   auto take = [&](size_t bytes) {
     char* d = c.arena + used;
-    used += pad(bytes);
+    used += pad256(bytes);
     return d;
   };
   for (size_t i = 0; i < k; i++) {
@@ -668,8 +653,8 @@ static void eval_multi_t(Ctx& c, const void* const* polys, const size_t* lens, s
   }
   // descriptors and the three tables travel as ONE host-to-device copy (they sit back to back in the arena; four copies from
   // pageable memory were four staged transfers of 10-20 us each in front of a 30 us kernel)
-  const size_t o_desc = 0, o_pts = o_desc + pad(k * sizeof(EvalPoly)), o_16 = o_pts + pad(m * 32), o_4096 = o_16 + pad(m * 256 * 32),
-               up_bytes = o_4096 + pad(m * 20 * 32);
+  const size_t o_desc = 0, o_pts = o_desc + pad256(k * sizeof(EvalPoly)), o_16 = o_pts + pad256(m * 32), o_4096 = o_16 + pad256(m * 256 * 32),
+               up_bytes = o_4096 + pad256(m * 20 * 32);
   char* d_up = take(up_bytes);
   EvalPoly* d_desc = (EvalPoly*)(d_up + o_desc);
   uint32_t* d_pts = (uint32_t*)(d_up + o_pts);
@@ -706,13 +691,7 @@ static void eval_multi_t(Ctx& c, const void* const* polys, const size_t* lens, s
 
 void fv_eval_multi(Ctx& c, int field, const void* const* polys, const size_t* lens, size_t k, const void* points, size_t m,
                    uint32_t flags, uint8_t* out) {
-  switch (field) {
-    case 0: eval_multi_t<0>(c, polys, lens, k, points, m, flags, out); break;
-    case 1: eval_multi_t<1>(c, polys, lens, k, points, m, flags, out); break;
-    case 2: eval_multi_t<2>(c, polys, lens, k, points, m, flags, out); break;
-    case 3: eval_multi_t<3>(c, polys, lens, k, points, m, flags, out); break;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { eval_multi_t<F()>(c, polys, lens, k, points, m, flags, out); });
 }
 
 // ---- sums without an eq factor (the classic sum-check rounds) ------------------------------------------------------
@@ -796,15 +775,14 @@ static void plain_sums_t(Ctx& c, const void* A, const void* B, const void* C, si
   const uint32_t h = (uint32_t)(len / 2);
   const uint32_t want = (h + 256 * 8 - 1) / (256 * 8);
   const uint32_t blocks = want < 1 ? 1 : (want > 2048 ? 2048 : want);
-  auto pad = [](size_t b) { return (b + 255) & ~(size_t)255; };
   size_t need = (size_t)blocks * 128 + 128 + 512;
-  if (!dev) need += pad(len * 32) * (KIND == 4 ? 3 : 2);
+  if (!dev) need += pad256(len * 32) * (KIND == 4 ? 3 : 2);
   arena_reserve(c, need);
   size_t used = 0;
   auto stage = [&](const void* p, size_t elems) -> const uint32_t* {
     if (dev) return (const uint32_t*)p;
     char* d = c.arena + used;
-    used += pad(elems * 32);
+    used += pad256(elems * 32);
     HIPCHK(hipMemcpyAsync(d, p, elems * 32, hipMemcpyHostToDevice, c.stream));
     return (const uint32_t*)d;
   };
@@ -812,7 +790,7 @@ static void plain_sums_t(Ctx& c, const void* A, const void* B, const void* C, si
   const uint32_t* dB = stage(B, len);
   const uint32_t* dC = KIND == 4 ? stage(C, len) : nullptr;
   uint32_t* partial = (uint32_t*)(c.arena + used);
-  used += pad((size_t)blocks * 128);
+  used += pad256((size_t)blocks * 128);
   uint32_t* dout = (uint32_t*)(c.arena + used);
   const bool prof = G.profiling;
   DeviceBackend be(c, false, prof);
@@ -842,41 +820,16 @@ static void plain_sums_t(Ctx& c, const void* A, const void* B, const void* C, si
 
 void fv_plain_sums(Ctx& c, int field, int kind, const void* A, const void* B, const void* C, size_t len, uint32_t flags,
                    uint8_t* out) {
-#define PLS(FID)                                                                  \
-  switch (kind) {                                                                 \
-    case 1: plain_sums_t<FID, 1>(c, A, B, C, len, flags, out); return;            \
-    case 2: plain_sums_t<FID, 2>(c, A, B, C, len, flags, out); return;            \
-    case 3: plain_sums_t<FID, 3>(c, A, B, C, len, flags, out); return;            \
-    case 4: plain_sums_t<FID, 4>(c, A, B, C, len, flags, out); return;            \
-    default: throw Fail{NMX_E_ARG, "bad sum-check kind"};                         \
-  }
-  switch (field) {
-    case 0: PLS(0)
-    case 1: PLS(1)
-    case 2: PLS(2)
-    case 3: PLS(3)
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
-#undef PLS
+  with_field(field, [&](auto F) {
+    with_index<1, 4>(kind, "bad sum-check kind", [&](auto M) { plain_sums_t<F(), M()>(c, A, B, C, len, flags, out); });
+  });
 }
 
 void fv_eq_sums(Ctx& c, int field, int mode, const void* A, const void* B, const void* C, size_t len, const void* eqL,
                 size_t nL, const void* eqR, size_t nR, uint32_t shift, uint32_t flags, uint8_t* out) {
-#define EQS(FID)                                                                                        \
-  switch (mode) {                                                                                       \
-    case 1: eq_sums_t<FID, 1>(c, A, B, C, len, eqL, nL, eqR, nR, shift, flags, out); return;            \
-    case 2: eq_sums_t<FID, 2>(c, A, B, C, len, eqL, nL, eqR, nR, shift, flags, out); return;            \
-    case 3: eq_sums_t<FID, 3>(c, A, B, C, len, eqL, nL, eqR, nR, shift, flags, out); return;            \
-    default: throw Fail{NMX_E_ARG, "bad sum-check mode"};                                               \
-  }
-  switch (field) {
-    case 0: EQS(0)
-    case 1: EQS(1)
-    case 2: EQS(2)
-    case 3: EQS(3)
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
-#undef EQS
+  with_field(field, [&](auto F) {
+    with_index<1, 3>(mode, "bad sum-check mode", [&](auto M) { eq_sums_t<F(), M()>(c, A, B, C, len, eqL, nL, eqR, nR, shift, flags, out); });
+  });
 }
 
 }  // namespace nmx

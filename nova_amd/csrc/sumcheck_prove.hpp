@@ -989,14 +989,14 @@ template <int FID> struct ScEqDev {
   uint32_t *heapL = nullptr, *heapR = nullptr;
   static size_t heap_bytes(uint32_t l_) {
     const uint32_t fh = l_ / 2, sh = l_ - fh, kl = fh > 0 ? fh - 1 : 0;
-    return ((((size_t)2 << kl) * 32 + 255) & ~(size_t)255) + ((size_t)2 << sh) * 32 + 512;
+    return pad256(((size_t)2 << kl) * 32) + ((size_t)2 << sh) * 32 + 512;
   }
   // builds the tables on the stream (no wait) into [mem, mem + heap_bytes(l))
   void init(ScDev<FID>& h, const typename ScAlg<FID>::Eq& eq, char* mem) {
     l = eq.l, first_half = eq.first_half, second_half = eq.second_half;
     KL = first_half > 0 ? first_half - 1 : 0, KR = second_half;
     heapL = (uint32_t*)mem;
-    heapR = (uint32_t*)(mem + ((((size_t)2 << KL) * 32 + 255) & ~(size_t)255));
+    heapR = (uint32_t*)(mem + pad256(((size_t)2 << KL) * 32));
     DeviceBackend be(h.c, false, false);
     uint32_t w[8] = {1, 0, 0, 0, 0, 0, 0, 0};  // ONE in the vectors' form
     if (h.mont) H::one().to_mont256(w);
@@ -1484,7 +1484,7 @@ static void sc_prove_batch_t(Ctx& c, const uint8_t* claims_b, const size_t* num_
     size_t heap_total = 0;
     for (size_t i = 0; i < k; i++) {
       require(num_rounds[i] >= 1 && num_rounds[i] < 31, NMX_E_ARG, "prove_batch_eval: 1 <= num_rounds < 31");
-      heap_total += (ScEqDev<FID>::heap_bytes((uint32_t)num_rounds[i]) + 255) & ~(size_t)255;
+      heap_total += pad256(ScEqDev<FID>::heap_bytes((uint32_t)num_rounds[i]));
     }
     arena_reserve(c, k * kScPartialBytes + 512);
     for (size_t i = 0; i < k; i++) HIPCHK(hipMemsetAsync(c.arena + (i + 1) * kScPartialBytes - 256, 0, 256, c.stream));  // the tickets
@@ -1506,7 +1506,7 @@ static void sc_prove_batch_t(Ctx& c, const uint8_t* claims_b, const size_t* num_
         dev.pass[i].to_host(dev.len[i], nullptr, out);
       } else {
         dev.eqd[i].init(h, cs[i].eq, c.aux + off);
-        off += (ScEqDev<FID>::heap_bytes((uint32_t)num_rounds[i]) + 255) & ~(size_t)255;
+        off += pad256(ScEqDev<FID>::heap_bytes((uint32_t)num_rounds[i]));
       }
     }
     // the claims of a round are independent passes over their own tables: claim i > 0 runs on side stream i - 1 (ordered behind
@@ -1577,13 +1577,7 @@ void fv_mle_multi_eval(Ctx& c, int field, const void* const* zs, size_t k, size_
                        uint32_t s_right, uint32_t flags, uint8_t* out) {
   require(k >= 1 && k <= kMailSlots, NMX_E_ARG, "mle_multi_eval: 1 .. 16 polynomials per pass");
   try {
-    switch (field) {
-      case 0: mle_multi_eval_t<0>(c, zs, k, len, eqL, eqR, s_right, flags, out); return;
-      case 1: mle_multi_eval_t<1>(c, zs, k, len, eqL, eqR, s_right, flags, out); return;
-      case 2: mle_multi_eval_t<2>(c, zs, k, len, eqL, eqR, s_right, flags, out); return;
-      case 3: mle_multi_eval_t<3>(c, zs, k, len, eqL, eqR, s_right, flags, out); return;
-      default: throw Fail{NMX_E_ARG, "bad field id"};
-    }
+    with_field(field, [&](auto F) { mle_multi_eval_t<F()>(c, zs, k, len, eqL, eqR, s_right, flags, out); });
   } catch (const ScFail& f) {
     rethrow(f);
   }
@@ -1591,29 +1585,15 @@ void fv_mle_multi_eval(Ctx& c, int field, const void* const* zs, size_t k, size_
 
 void fv_sumcheck_prove(Ctx& c, int field, int which, const void* claim, const void* taus, size_t num_rounds, void* A, void* B, void* C,
                        uint32_t flags, TranscriptFn cb, void* cb_ctx, uint8_t* out_polys, uint8_t* out_r, uint8_t* out_claims) {
-#define SCP(FID)                                                                                                              \
-  if (which == 3) sc_prove_t<FID, 3>(c, claim, taus, num_rounds, A, B, C, flags, cb, cb_ctx, out_polys, out_r, out_claims);   \
-  else sc_prove_t<FID, 4>(c, claim, taus, num_rounds, A, B, C, flags, cb, cb_ctx, out_polys, out_r, out_claims);              \
-  return;
-  switch (field) {
-    case 0: SCP(0)
-    case 1: SCP(1)
-    case 2: SCP(2)
-    case 3: SCP(3)
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
-#undef SCP
+  with_field(field, [&](auto F) {
+    if (which == 3) sc_prove_t<F(), 3>(c, claim, taus, num_rounds, A, B, C, flags, cb, cb_ctx, out_polys, out_r, out_claims);
+    else sc_prove_t<F(), 4>(c, claim, taus, num_rounds, A, B, C, flags, cb, cb_ctx, out_polys, out_r, out_claims);
+  });
 }
 void fv_sumcheck_prove_batch(Ctx& c, int field, const uint8_t* claims, const size_t* num_rounds, void* const* polys,
                              const uint8_t* const* eq_points, const uint8_t* coeffs, size_t k, uint32_t flags, TranscriptFn cb, void* cb_ctx,
                              uint8_t* out_polys, uint8_t* out_r, uint8_t* out_finals) {
-  switch (field) {
-    case 0: sc_prove_batch_t<0>(c, claims, num_rounds, polys, eq_points, coeffs, k, flags, cb, cb_ctx, out_polys, out_r, out_finals); return;
-    case 1: sc_prove_batch_t<1>(c, claims, num_rounds, polys, eq_points, coeffs, k, flags, cb, cb_ctx, out_polys, out_r, out_finals); return;
-    case 2: sc_prove_batch_t<2>(c, claims, num_rounds, polys, eq_points, coeffs, k, flags, cb, cb_ctx, out_polys, out_r, out_finals); return;
-    case 3: sc_prove_batch_t<3>(c, claims, num_rounds, polys, eq_points, coeffs, k, flags, cb, cb_ctx, out_polys, out_r, out_finals); return;
-    default: throw Fail{NMX_E_ARG, "bad field id"};
-  }
+  with_field(field, [&](auto F) { sc_prove_batch_t<F()>(c, claims, num_rounds, polys, eq_points, coeffs, k, flags, cb, cb_ctx, out_polys, out_r, out_finals); });
 }
 
 }  // namespace nmx
