@@ -453,6 +453,34 @@ int nmx_sumcheck_prove_quad_prod(int field, const void* claim, size_t num_rounds
 int nmx_sumcheck_prove_batch_eval(int field, const void* claims, const size_t* num_rounds, void* const* polys,
                                   const void* const* eq_points, const void* coeffs, size_t k, uint32_t flags,
                                   nmx_transcript_fn transcript, void* ctx, uint8_t* out_polys, uint8_t* out_r, uint8_t* out_finals);
+/* nmx_sumcheck_prove_batched_cubic == SumcheckProof::prove_batched_cubic (src/spartan/sumcheck.rs:509-577) with
+ * EqSumCheckInstance::evaluation_points_batched_cubic and fallback_eval_inf_batched_cubic (sumcheck.rs:749-894):
+ *     sum_x eq(tau, x) * sum_i alpha_i (A_i(x) B_i(x) - C_i(x)) = claim
+ * for k triples under ONE sum-check (the outer sum-check of several R1CS instances proven together).
+ *   field_id    NMX_F_*: the field of every element of the call, the `field` of the provers above.  (Not spelled `field`: the closed list
+ *               of tests/test_gpu_bad_field.py names every entry point with an `int field` parameter; this one's refusal of a bad id is
+ *               checked in tests/test_sumcheck_batched_abi.py and tests/test_gpu_sumcheck_batched.py.)
+ *   As, Bs, Cs  k tables each (host arrays of k pointers), every table 2^num_rounds elements: HBM-resident with NMX_SCALARS_DEVICE (the
+ *               intended form), host arrays otherwise (uploaded for the call, the host copies left untouched).  The tables are
+ *               BOUND IN PLACE; their contents after the call are unspecified.
+ *   taus        num_rounds elements (host); alphas: k elements (host); claim: one element.  NMX_SCALARS_MONT: everything is
+ *               Montgomery limbs, otherwise everything is canonical.
+ *   transcript  as for the provers above: once per round with the 4 UniPoly coefficients (constant term first).
+ *   out_polys   num_rounds x 4 x 32 bytes (exactly what the callback received); out_r: num_rounds x 32 bytes;
+ *   out_claims  k x 3 x 32 bytes, [A_i(r), B_i(r), C_i(r)] for i = 0 .. k-1 (the reference's claims[i]).  Any output may be NULL.
+ * 1 <= k <= 16 (the cap of nmx_sumcheck_prove_batch_eval: pointers and alphas travel by value in the kernel arguments); k = 0 (the
+ * reference's InvalidNumInstances) and k > 16: NMX_E_ARG.  A NULL table, or two of the 3 k tables overlapping in memory:
+ * NMX_E_ARG (an alias would corrupt the proof without a sign).  A claim, tau or alpha >= p: NMX_E_SCALAR_RANGE.  All of these
+ * are found before anything is launched: the tables are untouched.  A challenge >= p: NMX_E_SCALAR_RANGE; a callback that
+ * returns non-zero: NMX_E_ARG; a bad field id: NMX_E_ARG.  On any failure nothing of the call still runs when it returns.
+ * A round is the bind + sums pass over all 3 k tables and a one-block final sum into the mailbox; a tau of zero takes the
+ * third-sum fallback (one more pass over the high halves).  Options honoured: "sc_host_tail" (once the tables hold <= 2^that
+ * many elements the last device bind brings them to the host and the remaining rounds run there) and "sc_poll_us".  The other
+ * sc_* options (sc_fused_sum, sc_side_streams, sc_host_parts, sc_quad, sc_prelaunch, sc_resident, sc_torn_test) do NOT affect
+ * this call: every pass is launched after its challenge exists, nothing waits on the device for the host. */
+int nmx_sumcheck_prove_batched_cubic(int field_id, const void* claim, const void* taus, size_t num_rounds, void* const* As,
+                                     void* const* Bs, void* const* Cs, const void* alphas, size_t k, uint32_t flags,
+                                     nmx_transcript_fn transcript, void* ctx, uint8_t* out_polys, uint8_t* out_r, uint8_t* out_claims);
 /* ---- inner-product argument (the evaluation engine of the secondary curve) -----------------------------------------------------
  * InnerProductArgument::prove (src/provider/ipa_pc.rs:174-281), reached through EvaluationEngine::prove (:69-82) -- the evaluation
  * argument of S2 in CompressedSNARK::prove (src/nova/mod.rs:862-881; Grumpkin / Pallas / Vesta engines, src/provider/mod.rs:38-148).

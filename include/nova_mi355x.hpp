@@ -315,6 +315,23 @@ template <int FIELD> struct Sumcheck {
                                         &detail::round_cb<Transcript>, &tr, p.data(), r.data(), f.data()));
     return detail::unpack(nmax, 3, k, p, r, f);
   }
+  // SumcheckProof::prove_batched_cubic (sumcheck.rs:509-577): k <= 16 triples under one sum-check; claims = [A_0(r), B_0(r), C_0(r), A_1(r), ...]
+  template <class Transcript>
+  static SumcheckProof prove_batched_cubic(const Scalar& claim, const std::vector<Scalar>& taus, const std::vector<std::vector<Scalar>>& As,
+                                           const std::vector<std::vector<Scalar>>& Bs, const std::vector<std::vector<Scalar>>& Cs,
+                                           const std::vector<Scalar>& alphas, Transcript& tr, bool mont = false) {
+    const size_t l = taus.size(), k = As.size();
+    if (k == 0 || Bs.size() != k || Cs.size() != k || alphas.size() != k) throw std::invalid_argument("one B, C and alpha per A, at least one");
+    std::vector<void*> pa(k), pb(k), pc(k);
+    for (size_t i = 0; i < k; i++) {
+      if (As[i].size() != (size_t)1 << l || Bs[i].size() != As[i].size() || Cs[i].size() != As[i].size()) throw std::invalid_argument("tables must hold 2^taus.len() elements");
+      pa[i] = const_cast<Scalar*>(As[i].data()), pb[i] = const_cast<Scalar*>(Bs[i].data()), pc[i] = const_cast<Scalar*>(Cs[i].data());
+    }
+    std::vector<uint8_t> p(128 * l + 1), r(32 * l + 1), c(96 * k);
+    check(nmx_sumcheck_prove_batched_cubic(FIELD, claim.data(), taus.data(), l, pa.data(), pb.data(), pc.data(), alphas.data(), k,
+                                           mont ? NMX_SCALARS_MONT : 0u, &detail::round_cb<Transcript>, &tr, p.data(), r.data(), c.data()));
+    return detail::unpack(l, 4, 3 * k, p, r, c);
+  }
 };
 }  // namespace spartan
 
@@ -555,6 +572,16 @@ inline Proof prove_batch(int field, const std::vector<Scalar>& claims, const std
   Proof p{std::vector<uint8_t>(96 * nmax), std::vector<uint8_t>(32 * nmax), std::vector<uint8_t>(32 * claims.size())};
   check(nmx_sumcheck_prove_batch_eval(field, claims.data(), nr.data(), polys.data(), points.data(), coeffs.data(), claims.size(), kDev, cb, ctx,
                                       p.polys.data(), p.r.data(), p.claims.data()));
+  return p;
+}
+// prove_batched_cubic (sumcheck.rs:509-577) over 3 k HBM-resident tables (k <= 16, no two sharing memory); claims: k x [A_i(r), B_i(r), C_i(r)]
+inline Proof prove_batched_cubic(int field, const Scalar& claim, const std::vector<Scalar>& taus, const std::vector<void*>& As, const std::vector<void*>& Bs,
+                                 const std::vector<void*>& Cs, const std::vector<Scalar>& alphas, nmx_transcript_fn cb, void* ctx) {
+  const size_t l = taus.size(), k = As.size();
+  if (Bs.size() != k || Cs.size() != k || alphas.size() != k) throw std::invalid_argument("one B, C and alpha per A");
+  Proof p{std::vector<uint8_t>(128 * l), std::vector<uint8_t>(32 * l), std::vector<uint8_t>(96 * k)};
+  check(nmx_sumcheck_prove_batched_cubic(field, claim.data(), taus.data(), l, As.data(), Bs.data(), Cs.data(), alphas.data(), k, kDev, cb, ctx,
+                                         p.polys.data(), p.r.data(), p.claims.data()));
   return p;
 }
 // ck_c.scale(&r) (src/provider/ipa_pc.rs:190-191, pedersen.rs:499-506): one point times one scalar -- a commitment to the empty

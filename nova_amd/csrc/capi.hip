@@ -2736,6 +2736,51 @@ int nmx_sumcheck_prove_batch_eval(int field, const void* claims, const size_t* n
                             flags, transcript, ctx, out_polys, out_r, out_finals);
   });
 }
+// SumcheckProof::prove_batched_cubic (sumcheck.rs:509-577; sumcheck_batched.hpp).  Everything that can be refused is refused before a
+// device is leased: the tables are bound in place, so two of them sharing memory would corrupt the proof without a sign.
+int nmx_sumcheck_prove_batched_cubic(int field_id, const void* claim, const void* taus, size_t num_rounds, void* const* As, void* const* Bs,
+                                     void* const* Cs, const void* alphas, size_t k, uint32_t flags, nmx_transcript_fn transcript, void* ctx,
+                                     uint8_t* out_polys, uint8_t* out_r, uint8_t* out_claims) {
+  return guarded([&] {
+    check_sc_args(field_id, num_rounds, flags, transcript);
+    require(k >= 1 && k <= 16, NMX_E_ARG, "prove_batched_cubic: between 1 and 16 triples");
+    require(claim && (taus || num_rounds == 0) && As && Bs && Cs && alphas, NMX_E_ARG, "null argument");
+    const size_t n = (size_t)1 << num_rounds, bytes = n * 32;
+    std::vector<std::pair<uintptr_t, uintptr_t>> span;
+    for (size_t i = 0; i < k; i++)
+      for (void* const* T : {As, Bs, Cs}) {
+        require(T[i] != nullptr, NMX_E_ARG, "prove_batched_cubic: null table");
+        span.emplace_back((uintptr_t)T[i], (uintptr_t)T[i] + bytes);
+      }
+    std::sort(span.begin(), span.end());
+    for (size_t i = 1; i < span.size(); i++)
+      require(span[i - 1].second <= span[i].first, NMX_E_ARG, "prove_batched_cubic: two tables overlap (they are bound in place)");
+    with_field(field_id, [&](auto F) {
+      using Field = Fp<decltype(F)::value>;
+      auto lt_p = [](const void* p, size_t i) {
+        uint32_t w[8];
+        memcpy(w, (const uint8_t*)p + 32 * i, 32);
+        return Field::words_lt_p(w);
+      };
+      bool ok = lt_p(claim, 0);
+      for (size_t i = 0; i < num_rounds; i++) ok = ok && lt_p(taus, i);
+      for (size_t i = 0; i < k; i++) ok = ok && lt_p(alphas, i);
+      require(ok, NMX_E_SCALAR_RANGE, "prove_batched_cubic: claim / tau / alpha >= field modulus");
+    });
+    // (k and the scalars are checked again below the lease -- fv_sumcheck_prove_batched_cubic's require, ScAlg::in -- on purpose: those layers
+    // do not rely on their caller; the checks here are what makes a refused call need no device and launch nothing)
+    CtxLease L;
+    ScStaged st;
+    std::vector<void*> staged;
+    if (!(flags & NMX_SCALARS_DEVICE)) {
+      for (void* const* T : {As, Bs, Cs})
+        for (size_t i = 0; i < k; i++) staged.push_back(st.up(*L.c, T[i], n));
+      As = staged.data(), Bs = staged.data() + k, Cs = staged.data() + 2 * k;
+      flags |= NMX_SCALARS_DEVICE;
+    }
+    fv_sumcheck_prove_batched_cubic(*L.c, field_id, claim, taus, num_rounds, As, Bs, Cs, alphas, k, flags, transcript, ctx, out_polys, out_r, out_claims);
+  });
+}
 
 // Device state of one call that has to outlive the MSMs the call runs (they re-carve the context's arena): the context's aux buffer
 // up to kAuxMax bytes, an allocation of the call's own above that; carved front to back.  `ev`, if the call creates it, goes with it.

@@ -793,6 +793,9 @@ void fv_sumcheck_prove(Ctx&, int field, int which, const void* claim, const void
 void fv_sumcheck_prove_batch(Ctx&, int field, const uint8_t* claims, const size_t* num_rounds, void* const* polys,
                              const uint8_t* const* eq_points, const uint8_t* coeffs, size_t k, uint32_t flags, TranscriptFn cb, void* cb_ctx,
                              uint8_t* out_polys, uint8_t* out_r, uint8_t* out_finals);
+void fv_sumcheck_prove_batched_cubic(Ctx&, int field, const void* claim, const void* taus, size_t num_rounds, void* const* As, void* const* Bs,
+                                     void* const* Cs, const void* alphas, size_t k, uint32_t flags, TranscriptFn cb, void* cb_ctx,
+                                     uint8_t* out_polys, uint8_t* out_r, uint8_t* out_claims);  // sumcheck_batched.hpp
 
 const CurveOps& curve_ops_bn254_g1();
 const CurveOps& curve_ops_grumpkin();

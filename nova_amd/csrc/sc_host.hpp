@@ -8,6 +8,7 @@
 //   evaluation_points_cubic_with_three_inputs / quadratic_with_one_input     sumcheck.rs:900-970, 1039-1083
 //   fallback_eval_inf_three_inputs / _one_input (tau = 0)                    sumcheck.rs:1085-1136, 1185-1222
 //   compute_eval_points_quad_prod                                            sumcheck.rs:163-186
+//   evaluation_points_batched_cubic / fallback_eval_inf_batched_cubic        sumcheck.rs:749-894
 //   UniPoly::from_evals_deg2 / _deg3 / evaluate                              polys/univariate.rs:90-113, 140-149
 //   SumcheckProof::update_claim                                              sumcheck.rs:68-75
 //   MultilinearPolynomial::bind_poly_var_top                                 polys/multilinear.rs:65-84
@@ -265,6 +266,44 @@ void sc_tail_rounds(const ScAlg<FID>& alg, typename ScAlg<FID>::Eq* eq, uint32_t
       ScAlg<FID>::bind_top(C, r);
       eq->bound(r);
     }
+  }
+}
+
+// The rounds j0 .. l of prove_batched_cubic (sumcheck.rs:509-577) over HOST tables: K triples (A_i, B_i, C_i) of the current length
+// under one eq instance, t(X) = sum_i alpha_i (A_i(X) B_i(X) - C_i(X)).  evaluation_points_batched_cubic (sumcheck.rs:749-835) adds
+// the alpha-weighted terms up per index and multiplies by the eq factor once; here each triple's eq-factored sums (eq_sums, the
+// cubic prover's) are combined with the alphas afterwards -- the same field elements, K + 1 products per round more than the
+// reference's order instead of a second loop nest.  With tau_j = 0 the third sum t(-1) (fallback_eval_inf_batched_cubic,
+// sumcheck.rs:837-894) is combined the same way.  On return every table holds one element: claims[i] = [A_i(r), B_i(r), C_i(r)].
+template <int FID>
+void sc_tail_rounds_batched(const ScAlg<FID>& alg, typename ScAlg<FID>::Eq* eq, uint32_t l, uint32_t j0, typename ScAlg<FID>::H& claim,
+                            std::vector<std::vector<typename ScAlg<FID>::H>>& A, std::vector<std::vector<typename ScAlg<FID>::H>>& B,
+                            std::vector<std::vector<typename ScAlg<FID>::H>>& C, const std::vector<typename ScAlg<FID>::H>& alphas,
+                            TranscriptFn cb, void* cb_ctx, uint8_t* out_polys, uint8_t* out_r) {
+  using H = typename ScAlg<FID>::H;
+  const size_t k = alphas.size();
+  for (uint32_t j = j0; j <= l; j++) {
+    const std::vector<H> fac = eq->factors(j);
+    H t0 = H::zero(), tinf = H::zero(), s0, lead, sm1, co[4];
+    for (size_t i = 0; i < k; i++) {
+      H a0, ainf;
+      ScAlg<FID>::eq_sums(3, false, A[i], B[i], C[i], fac, &a0, &ainf);
+      t0 = t0 + alphas[i] * a0, tinf = tinf + alphas[i] * ainf;
+    }
+    eq->derive(t0, tinf, claim, false, s0, lead, sm1, [&] {
+      H tm1 = H::zero();
+      for (size_t i = 0; i < k; i++) {
+        H am1;
+        ScAlg<FID>::eq_sums(3, true, A[i], B[i], C[i], fac, &am1, nullptr);
+        tm1 = tm1 + alphas[i] * am1;
+      }
+      return tm1;
+    });
+    ScAlg<FID>::from_evals_deg3(s0, claim, lead, sm1, co);
+    const H r = alg.ask(cb, cb_ctx, co, 4, out_polys ? out_polys + 128 * (size_t)(j - 1) : nullptr, out_r ? out_r + 32 * (size_t)(j - 1) : nullptr);
+    claim = ScAlg<FID>::poly_eval(co, 4, r);
+    for (size_t i = 0; i < k; i++) ScAlg<FID>::bind_top(A[i], r), ScAlg<FID>::bind_top(B[i], r), ScAlg<FID>::bind_top(C[i], r);
+    eq->bound(r);
   }
 }
 

@@ -835,5 +835,6 @@ void fv_eq_sums(Ctx& c, int field, int mode, const void* A, const void* B, const
 }  // namespace nmx
 
 #include "sumcheck_prove.hpp"
+#include "sumcheck_batched.hpp"
 #include "ipa.hpp"
 #include "ipa_verify.hpp"

@@ -508,6 +508,34 @@ def sumcheck_prove_batch_eval(field, claims, num_rounds, polys, eq_points, coeff
     return _rows(out_p, nmax, 3), [x[0] for x in _rows(r, nmax, 1)], [x[0] for x in _rows(fin, k, 1)]
 
 
+def sumcheck_prove_batched_cubic(field, claim, taus, As, Bs, Cs, alphas, transcript, mont=False, ctx=None):
+    """SumcheckProof::prove_batched_cubic (src/spartan/sumcheck.rs:509-577): sum_x eq(tau, x) sum_i alpha_i (A_i B_i - C_i)(x) = claim for
+    k = len(As) <= 16 triples under one sum-check.  As, Bs, Cs: k tables each of 2^len(taus) elements -- CUDA tensors, bound IN PLACE
+    (contents unspecified afterwards), or host arrays (uploaded for the call, left untouched); two tables must not share memory.  taus,
+    alphas, claim: host.  Returns (round polynomials [rounds][4], challenges [rounds], [[A_i(r), B_i(r), C_i(r)] for i]) as 32-byte
+    strings."""
+    import ctypes
+    k = len(As)
+    assert k == len(Bs), "assert_eq!(k, polys_B.len())"
+    assert k == len(Cs), "assert_eq!(k, polys_C.len())"
+    al = _host_u8(alphas, 32)
+    assert k == al.size // 32, "assert_eq!(k, alphas.len())"
+    t = _host_u8(taus, 32)
+    nr = t.size // 32
+    parts = [_vec(x) for x in list(As) + list(Bs) + list(Cs)]
+    dev = parts[0][2] if parts else False
+    assert all(pt[2] == dev for pt in parts), "all tables in HBM or all on the host"
+    assert all(pt[1] == (1 << nr) for pt in parts), "every table holds 2^len(taus) elements"
+    ptrs = [(ctypes.c_void_p * max(k, 1))(*[pt[0] for pt in parts[w * k:(w + 1) * k]]) for w in range(3)]
+    cl = _chal(claim)
+    polys, r, out = np.zeros(128 * max(nr, 1), np.uint8), np.zeros(32 * max(nr, 1), np.uint8), np.zeros(96 * max(k, 1), np.uint8)
+    cb = as_transcript(transcript)
+    _check(L.lib().nmx_sumcheck_prove_batched_cubic(field, cl.ctypes.data, t.ctypes.data if nr else None, nr, ptrs[0], ptrs[1], ptrs[2],
+                                                   al.ctypes.data if k else None, k, _flags(dev, mont), cb, ctx, polys.ctypes.data,
+                                                   r.ctypes.data, out.ctypes.data))
+    return _rows(polys, nr, 4), [x[0] for x in _rows(r, nr, 1)], _rows(out, k, 3)
+
+
 # ---- R1CSShape::is_sat / is_sat_relaxed as one call (nmx_r1cs_is_sat; src/r1cs/mod.rs:474-574) -----------------------------------
 class SatResult:
     """Answer of r1cs_is_sat / r1cs_is_sat_relaxed.  `ok` is the reference's Ok(()); eq_ok false is its UnSat "... is unsatisfiable",
