@@ -558,6 +558,34 @@ int nmx_poly_suffix_horner(int field, const void* f, size_t n, const void* u, ui
  * `points` and `out` are host arrays; the coefficient vectors follow NMX_SCALARS_DEVICE. */
 int nmx_poly_eval_multi(int field, const void* const* polys, const size_t* lens, size_t k, const void* points, size_t m,
                         uint32_t flags, uint8_t* out);
+/* ---- Mercury's prover passes (the second evaluation engine on BN254, src/provider/mercury.rs) -----------------------------------
+ * The two passes over all N coefficients of f between Mercury's commitments that no other call expresses; f is viewed as an
+ * n_rows x n_cols matrix, row-major (the reference calls with n_cols = b = sqrt(N) and n_rows = b, or b / 2 when log N is odd,
+ * mercury.rs:919-931).  The third N-sized pass, quot_f (mercury.rs:1163-1180), composes from nmx_field_lincomb_powers over [f, q] with
+ * s = -(zeta^b - alpha) and nmx_poly_suffix_horner at zeta: out[1..n) is quot_f and out[0] must equal g(zeta) (the reference's
+ * assert_eq!(rem, ZERO)); INTEGRATION.md 2l.  Any n_rows >= 1, n_cols >= 1: no power of two, no n_rows <= n_cols is required.
+ * Flags: NMX_SCALARS_MONT (the vectors and alpha are Montgomery limbs), NMX_SCALARS_DEVICE (EVERY vector pointer, the outputs included,
+ * is HBM; otherwise host arrays are staged through the context's workspace), NMX_ASYNC (with HBM operands only, as for
+ * nmx_poly_fold_pairs); any other flag: NMX_E_ARG.  `alpha` is always a host pointer.  As for nmx_poly_suffix_horner, coefficients
+ * (and eq_col) may be any 256-bit words and the outputs are canonical (< p, in the form of the inputs).
+ * Errors, all found before a device is touched, and on any error nothing is written: a NULL pointer (other than out_q with
+ * n_rows == 1), n_rows == 0 or n_cols == 0, a field_id that is none of NMX_F_*: NMX_E_ARG; n_rows * n_cols overflowing or >= 2^32:
+ * NMX_E_TOO_LARGE; alpha >= p: NMX_E_SCALAR_RANGE; overlapping buffers: NMX_E_ARG -- out_q or out_g with f, out_q with out_g, out_h
+ * with f or with eq_col (the nmx_poly_suffix_horner rule: every q element depends on rows that other waves still read). */
+/* h[row] = sum_{col < n_cols} f[row * n_cols + col] * eq_col[col],  row < n_rows      (compute_h_poly, mercury.rs:369-386, called at :966) */
+int nmx_mercury_h_poly(int field_id, const void* f, size_t n_rows, size_t n_cols, const void* eq_col,
+                       uint32_t flags, void* out_h /* n_rows */);
+/* f(X) = (X^n_cols - alpha) q(X) + g(X), f of n_rows * n_cols coefficients, low to high (divide_by_binomial, mercury.rs:319-356 with
+ * divide_by_linear_polynomial :281-288 and transpose :291-312, called at :995):
+ *   g[c]              = sum_{j < n_rows}      f[j * n_cols + c] * alpha^j            c < n_cols
+ *   q[k * n_cols + c] = sum_{k < j < n_rows}  f[j * n_cols + c] * alpha^(j - k - 1)  k < n_rows - 1
+ * q is written in the layout the reference holds AFTER its transpose, as exactly (n_rows - 1) * n_cols elements: the reference's b * b
+ * vector before trim() without its all-zero tail.  The reference's trim() may drop further zero top coefficients; those change neither
+ * commit(ck, q) nor the later batch_add, so the caller may skip it.  n_rows == 1: q is empty (out_q may be NULL) and g = f.
+ * The rows are cut into segments (three launches: local totals, carries, the walk that writes q); option "mercury_seg_rows"
+ * of nmx_set_option sets the rows per segment (0 = by size) and never changes a result. */
+int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, size_t n_cols, const void* alpha,
+                                   uint32_t flags, void* out_q /* (n_rows - 1) * n_cols */, void* out_g /* n_cols */);
 /* EqPolynomial::evals_from_points (src/spartan/polys/eq.rs:54-73): out[2^ell] = eq(r, x) for x in {0,1}^ell, r[0] the
  * most significant variable.  r: ell x 32 bytes, host.  out: host, or HBM with NMX_SCALARS_DEVICE. */
 int nmx_eq_evals_from_points(int field, const void* r, size_t ell, uint32_t flags, void* out);
@@ -683,6 +711,8 @@ int nmx_set_window_bits(uint32_t c);
  * round of the single-pass scan, 64; 1..63 force its multi-round path in tests), "horner_sub" (512-coefficient sub-tiles per
  * wave of the scan: 0 = by size, 1, 2, 4), "eq_max_blocks" (grid cap of the eq-factored sum passes: 0 = 768 for evaluate_with, 2048 otherwise), "horner_spin_limit" (polls before a wave of the scan gives up and the call falls back
  * to the two-pass kernels: 0 = 2^22; tests set 1),
+ * "mercury_seg_rows" (rows per segment of nmx_mercury_divide_by_binomial's kernels: 0 = by size; tests force the multi-segment path
+ * at tiny shapes),
  * "host_split" / "host_split_min_n" (an MSM with HOST scalars over at least host_split_min_n = 2^19 pairs of a key on one device is cut
  * into contiguous pieces (host_split = 255, the default: 2 / 3 / 4 pieces from 2^19 / 2^20 / 2^21 pairs; 2..16: that many) -- the
  * reference's own chunk + reduce decomposition, src/provider/msm.rs:564-574 -- so that piece i's scalars cross PCIe while piece

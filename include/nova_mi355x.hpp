@@ -550,6 +550,24 @@ inline std::vector<Scalar> poly_eval_multi(int field, const std::vector<const vo
   check(nmx_poly_eval_multi(field, polys.data(), lens.data(), polys.size(), pts.data(), pts.size(), kDev, out[0].data()));
   return out;
 }
+// Mercury's N-sized prover passes over an HBM-resident f of n_rows * n_cols coefficients (mercury.rs:966, :995, :1163-1180)
+inline void mercury_h_poly(int field, const void* f, size_t n_rows, size_t n_cols, const void* eq_col, void* out_h) {  // compute_h_poly; out_h: n_rows
+  check(nmx_mercury_h_poly(field, f, n_rows, n_cols, eq_col, kAsync, out_h));
+}
+// divide_by_binomial: out_q (n_rows - 1) * n_cols elements (the reference's layout after its transpose, without the zero tail), out_g n_cols
+inline void mercury_divide_by_binomial(int field, const void* f, size_t n_rows, size_t n_cols, const Scalar& alpha, void* out_q, void* out_g) {
+  check(nmx_mercury_divide_by_binomial(field, f, n_rows, n_cols, alpha.data(), kAsync, out_q, out_g));
+}
+// the quot_f block from calls that exist.  neg_zeta_b_alpha = -(zeta^b - alpha), the scalar the reference hands to batch_add_with_polynomials
+// (:1171); tmp and out: n elements each.  out[1..n) is quot_f; the returned out[0] must equal g(zeta) (the reference's assert_eq!(rem, ZERO)).
+inline Scalar mercury_quot_f(int field, const void* f, size_t n, const void* q, size_t n_q, const Scalar& neg_zeta_b_alpha, const Scalar& zeta, void* tmp,
+                             void* out) {
+  lincomb_powers(field, {f, q}, {n, n_q}, neg_zeta_b_alpha, n, tmp);
+  suffix_horner(field, tmp, n, zeta, out);
+  // out[0] comes back through the library (this header includes no HIP runtime and so has no device-to-host copy of its own): the
+  // one-coefficient polynomial {out[0]} evaluated at 0 is out[0]
+  return poly_eval_multi(field, {out}, {1}, {Scalar{}})[0];
+}
 // the sum-check provers over HBM-resident tables (bound in place); `cb` / `ctx`: nmx_transcript_fn and its state
 struct Proof {
   std::vector<uint8_t> polys, r, claims;

@@ -2329,6 +2329,49 @@ int nmx_poly_suffix_horner(int field, const void* f, size_t n, const void* u, ui
   });
 }
 
+// ---- Mercury's prover passes (mercury.hpp; src/provider/mercury.rs:369-386 and :319-356) ----------------------------------------------
+// Everything that can be refused is refused before a device is leased: a refused call needs no device, launches nothing, writes nothing.
+static size_t mercury_check_shape(int field_id, size_t n_rows, size_t n_cols, uint32_t flags) {
+  require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_ASYNC)) == 0, NMX_E_ARG,
+          "nmx_mercury_*: only NMX_SCALARS_MONT, NMX_SCALARS_DEVICE and NMX_ASYNC apply");
+  with_field(field_id, [](auto) {});
+  require(n_rows >= 1 && n_cols >= 1, NMX_E_ARG, "nmx_mercury_*: n_rows and n_cols must be at least 1");
+  require(n_rows < (1ull << 32) && n_cols < (1ull << 32) && (uint64_t)n_rows * (uint64_t)n_cols < (1ull << 32), NMX_E_TOO_LARGE,
+          "nmx_mercury_*: n_rows * n_cols must stay below 2^32");
+  return n_rows * n_cols;
+}
+static bool mercury_overlap(const void* a, size_t a_elems, const void* b, size_t b_elems) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a_elems && b_elems && x < y + b_elems * 32 && y < x + a_elems * 32;
+}
+int nmx_mercury_h_poly(int field_id, const void* f, size_t n_rows, size_t n_cols, const void* eq_col, uint32_t flags, void* out_h) {
+  return guarded([&] {
+    const size_t n = mercury_check_shape(field_id, n_rows, n_cols, flags);
+    require(f && eq_col && out_h, NMX_E_ARG, "null argument");
+    require(!mercury_overlap(out_h, n_rows, f, n) && !mercury_overlap(out_h, n_rows, eq_col, n_cols), NMX_E_ARG,
+            "nmx_mercury_h_poly: out_h overlaps f or eq_col");
+    CtxLease L;
+    fv_mercury_h_poly(*L.c, field_id, f, n_rows, n_cols, eq_col, flags, out_h);
+  });
+}
+int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, size_t n_cols, const void* alpha, uint32_t flags,
+                                   void* out_q, void* out_g) {
+  return guarded([&] {
+    const size_t n = mercury_check_shape(field_id, n_rows, n_cols, flags), nq = n - n_cols;
+    require(f && alpha && out_g && (out_q || n_rows == 1), NMX_E_ARG, "null argument");
+    // never in place: every q element depends on rows that other waves still read, and the second walk re-reads f after q was written
+    require(!mercury_overlap(out_q, nq, f, n) && !mercury_overlap(out_g, n_cols, f, n) && !mercury_overlap(out_q, nq, out_g, n_cols),
+            NMX_E_ARG, "nmx_mercury_divide_by_binomial: out_q / out_g overlap f or each other");
+    with_field(field_id, [&](auto F) {
+      uint32_t w[8];
+      memcpy(w, alpha, 32);
+      require(Fp<decltype(F)::value>::words_lt_p(w), NMX_E_SCALAR_RANGE, "nmx_mercury_divide_by_binomial: alpha >= field modulus");
+    });
+    CtxLease L;
+    fv_mercury_divide_by_binomial(*L.c, field_id, f, n_rows, n_cols, alpha, flags, out_q, out_g);
+  });
+}
+
 int nmx_poly_eval_multi(int field, const void* const* polys, const size_t* lens, size_t k, const void* points, size_t m,
                         uint32_t flags, uint8_t* out) {
   return guarded([&] {
@@ -3204,6 +3247,7 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "horner_top") G.horner_top = value;
     else if (n == "horner_window") G.horner_window = value ? value : 64u;
     else if (n == "horner_sub") G.horner_sub = value;
+    else if (n == "mercury_seg_rows") G.mercury_seg_rows = value;
     else if (n == "eq_max_blocks") G.eq_max_blocks = value;
     else if (n == "horner_spin_limit") G.horner_spin_limit = value;
     else if (n == "seg_heavy_above") G.seg_heavy_above = value > 63u ? 63u : value;

@@ -1909,3 +1909,4 @@ void fv_bind(Ctx& c, int field, const void* z, size_t z_len, size_t lo_off, size
 }  // namespace nmx
 
 #include "r1cs_eval.hpp"
+#include "mercury.hpp"

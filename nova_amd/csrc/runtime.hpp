@@ -332,6 +332,7 @@ struct Global {
   std::atomic<uint32_t> horner_sub{0};            // option horner_sub: 512-coefficient sub-tiles per wave of the single-pass scan (0 = by size, 1, 2, 4)
   std::atomic<uint32_t> horner_spin_limit{0};     // option horner_spin_limit: polls before a wave of the scan gives up (0 = 2^22; tests set 1 to force the fall-back)
   std::atomic<uint32_t> horner_window{64};        // option horner_window: tiles per look-back round of the single-pass scan (tests: 1 .. 63 force the multi-round path)
+  std::atomic<uint32_t> mercury_seg_rows{0};      // option mercury_seg_rows: rows per segment of Mercury's division kernels (mercury.hpp mercury_plan; 0 = by size; tests force the multi-segment path at tiny shapes)
   std::atomic<uint32_t> seg_heavy_above{0};       // env NMX_TUNE_SEG_HEAVY_ABOVE / option seg_heavy_above: 0 = by pieces per bucket (8 or 12)
   std::atomic<uint32_t> prefix_tables{2};         // env NMX_TUNE_PREFIX_TABLES / option prefix_tables: narrower table sets over a key's first points (capi.hip add_prefix_tables): 0 none, 1 the 2^18-point set of wide-table keys only, 2 the whole chain (batches descend it)
   std::atomic<uint32_t> no_batch_fuse{0};         // env NMX_TUNE_NO_BATCH_FUSE / option no_batch_fuse: every vector of a batch runs alone
@@ -737,6 +738,11 @@ void fv_r1cs_sat(Ctx&, int field, const CsrView (&abc)[3], const void* W, size_t
 // of k x 32 bytes in the same form.  Synchronous.  rows <= 2^ell_x and cols <= 2^ell_y are the caller's to check.
 void fv_r1cs_evaluate(Ctx&, int field, const CsrView* mats, size_t k, const void* r_x, uint32_t ell_x, const void* r_y,
                       uint32_t ell_y, uint32_t flags, uint8_t* out);
+// Mercury's prover passes (mercury.hpp): h[row] = <f[row], eq_col>; q, g of f(X) / (X^n_cols - alpha).  Vectors follow NMX_SCALARS_DEVICE,
+// alpha is a host pointer; NMX_ASYNC with HBM operands.  Shapes, NULLs and overlaps are the caller's to check.
+void fv_mercury_h_poly(Ctx&, int field, const void* f, size_t n_rows, size_t n_cols, const void* eq_col, uint32_t flags, void* out_h);
+void fv_mercury_divide_by_binomial(Ctx&, int field, const void* f, size_t n_rows, size_t n_cols, const void* alpha, uint32_t flags,
+                                   void* out_q, void* out_g);
 void fv_nifs_fold(Ctx&, int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e, const void* r,
                   uint32_t flags, void* w, void* e);
 void fv_eq_evals(Ctx&, int field, const void* r_host, uint32_t ell, uint32_t flags, uint32_t* d_out);

@@ -429,6 +429,50 @@ def div_by_monomial(field, f, u, mont=False):
     return suffix_horner(field, f, u, mont)[1:]
 
 
+# ---- Mercury's prover passes (src/provider/mercury.rs): the N-sized steps between its commitments -------------------------------
+FIELD_MODULUS = {BN254_FQ: 0x30644e72e131a029b85045b68181585d97816a916871ca8d3c208c16d87cfd47,
+                 BN254_FR: 0x30644e72e131a029b85045b68181585d2833e84879b9709143e1f593f0000001,
+                 PASTA_FP: 0x40000000000000000000000000000000224698fc094cf91b992d30ed00000001,
+                 PASTA_FQ: 0x40000000000000000000000000000000224698fc0994a8dd8c46eb2100000001}
+
+
+def mercury_h_poly(field, f, n_rows, n_cols, eq_col, mont=False, async_=False):
+    """compute_h_poly (mercury.rs:369-386): h[row] = sum_col f[row * n_cols + col] * eq_col[col], f viewed as n_rows x n_cols."""
+    pf, n, dev, _kf = _vec(f)
+    pe, ne, deve, _ke = _vec(eq_col)
+    assert n == n_rows * n_cols and ne == n_cols and dev == deve, "f is n_rows x n_cols, eq_col has n_cols entries, both host or both HBM"
+    po, out = _out_like(dev, n_rows, f)
+    _check(L.lib().nmx_mercury_h_poly(field, pf, n_rows, n_cols, pe, _flags(dev, mont, async_), po))
+    return out
+
+
+def mercury_divide_by_binomial(field, f, n_rows, n_cols, alpha, mont=False, async_=False):
+    """divide_by_binomial (mercury.rs:319-356): f(X) = (X^n_cols - alpha) q(X) + g(X) -> (q, g); q has (n_rows - 1) * n_cols elements in the
+    reference's layout after its transpose (its b * b vector before trim() without the all-zero tail), g has n_cols."""
+    pf, n, dev, _kf = _vec(f)
+    assert n == n_rows * n_cols, "f is n_rows x n_cols"
+    aa = _chal(alpha)
+    pq, q = _out_like(dev, (n_rows - 1) * n_cols, f)
+    pg, g = _out_like(dev, n_cols, f)
+    _check(L.lib().nmx_mercury_divide_by_binomial(field, pf, n_rows, n_cols, aa.ctypes.data, _flags(dev, mont, async_), pq if n_rows > 1 else None, pg))
+    return q, g
+
+
+def mercury_quot_f(field, f, q, zeta_b_minus_alpha, zeta, mont=False):
+    """The quot_f block (mercury.rs:1163-1180) from calls that exist: f - (zeta^b - alpha) q through lincomb_powers over [f, q] with
+    s = -(zeta^b - alpha), then suffix_horner at zeta -> (quot, rem).  quot = out[1:] is (f - (zeta^b - alpha) q - g(zeta)) / (X - zeta): it
+    does not depend on coefficient 0, so the reference's `coeffs[0] -= g_zeta` never has to touch the vector; rem = out[0] (32 bytes) must
+    equal g(zeta), which restates the reference's assert_eq!(rem, ZERO) -- the caller compares."""
+    p = FIELD_MODULUS[field]
+    z = int.from_bytes(_chal(zeta_b_minus_alpha).tobytes(), "little")
+    assert z < p, "zeta^b - alpha >= field modulus"
+    s = ((p - z) % p).to_bytes(32, "little")      # -x is p - x in the canonical and in the Montgomery form alike
+    pq, nq, _dq, _kq = _vec(q)
+    t = lincomb_powers(field, [f, q] if nq else [f], s, mont=mont)
+    out = suffix_horner(field, t, zeta, mont)
+    return out[1:], (out[0].cpu().numpy() if _is_device_tensor(out) else out[0]).tobytes()
+
+
 # ---- Spartan's sum-check provers, one call each (nmx_sumcheck_prove_*; src/spartan/sumcheck.rs:199-507) ---------------------
 def as_transcript(fn):
     """fn(list of 32-byte coefficient strings) -> 32-byte challenge, wrapped as nmx_transcript_fn.  The transcript (Keccak on
