@@ -597,7 +597,12 @@ int nmx_mle_multi_evaluate(int field, const void* const* zs, size_t k, size_t le
                            uint32_t flags, uint8_t* out);
 /* SparseMatrix (CSR, scipy naming: data / indices / indptr, src/r1cs/sparse.rs:232-260) resident in HBM, and
  * SparseMatrix::multiply_vec (sparse.rs:201-229): out[rows] = M * z.  indptr / indices are `usize` on the reference
- * side, hence uint64_t here.  R1CS matrices are fixed per circuit: register once, apply every step. */
+ * side, hence uint64_t here.  R1CS matrices are fixed per circuit: register once, apply every step.
+ * The gathered vector of a product over a registered matrix (z / x of nmx_spmv_apply, _pair, _transposed, _many, and z1 of
+ * nmx_r1cs_cross_term when z2 is NULL) may hold ANY 256-bit words: a word w counts as w mod p, the outputs are canonical (< p) and
+ * equal the product over the reduced words, in the canonical and in the Montgomery layout alike (there
+ * out_word = sum coefficient * (w mod p) mod p).  E and u of nmx_r1cs_cross_term and nmx_r1cs_is_sat are NOT covered by this: they
+ * must be < p, the default stated at the top of this header. */
 int nmx_spmv_register(int field, const uint64_t* indptr, const uint64_t* indices, const void* data, size_t rows,
                       size_t cols, uint32_t flags, uint64_t* handle);
 int nmx_spmv_unregister(uint64_t handle);

@@ -19,6 +19,7 @@ import pytest
 from oracle import pyref as R
 from tests import fv_common as C
 from tests import r1cs_eval_common as V
+from tests.spmv_edges_common import coefficient_class
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SRC = os.path.join(ROOT, "tests", "cpp", "r1cs_eval_mirror_test.cpp")
@@ -151,19 +152,6 @@ def E():
 
 
 RI = 1 << 261  # the internal residue form: x * 2^261 mod p (nova_amd/csrc/fp.hpp)
-
-
-def coefficient_class(p, v):
-    """SpmvClassifyFn (nova_amd/csrc/fieldvec.hip): 0 general, 1 +1, 2 -1, 3..8 +2..+7, 9..14 -2..-7"""
-    if v == 1:
-        return 1
-    if 2 <= v <= 7:
-        return v + 1
-    if p - v == 1:
-        return 2
-    if 2 <= p - v <= 7:
-        return p - v + 7
-    return 0
 
 
 def u32_words(vals):
