@@ -726,6 +726,9 @@ int nmx_set_window_bits(uint32_t c);
  * entries per four-lane group, default 8; 0 = the task path: plan, expand, accumulate, strided folds),
  * "seg_heavy_above" (pieces per bucket summed without a pre-fold pass: 0 = by table width, else 1..63), "no_tree_fuse" (bucket
  * reduction: 0 = fused levels or one launch per level by the box's measured launch gap, 1 = one launch per level, 2 = fused),
+ * "reduce_form" (bucket reduction: 0 = by bucket count, 1 = the (D, Y) pair tree, 2 = bit-sliced sums -- the pair-sum tree, the sums of
+ * its odd nodes per level and one pairwise combine at the end; other values: NMX_E_ARG),
+ * "no_clean_accum" (1: keys without identity points also run the segment accumulate that tests every gathered row for the identity),
  * "hist_grid" (blocks of the partition's counting pass; 0 = as the placing pass: measured flat, profiles/r03_msm_2p20/tail_ab.txt),
  * "shard_min_n", "cache_table_after", "max_table_mib" (see the sections above), "force_peer_copy" (1: the HBM-resident scalars of
  * a sharded call are staged through hipMemcpyPeerAsync even when the shard sits on the source GPU: exercises the cross-device

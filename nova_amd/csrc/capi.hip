@@ -160,6 +160,12 @@ static void ensure_init() {
   if (const char* t = getenv("NMX_TUNE_NO_BATCH_FUSE")) G.no_batch_fuse = (uint32_t)atoi(t);
   if (const char* t = getenv("NMX_TUNE_PREFIX_TABLES")) G.prefix_tables = (uint32_t)atoi(t);
   if (const char* t = getenv("NMX_TUNE_NO_TREE_FUSE")) G.no_tree_fuse = (uint32_t)atoi(t);
+  if (const char* t = getenv("NMX_TUNE_NO_CLEAN_ACCUM")) G.no_clean_accum = (uint32_t)atoi(t);
+  if (const char* t = getenv("NMX_TUNE_REDUCE_FORM")) {
+    const int v = atoi(t);
+    require(v >= 0 && v <= 2, NMX_E_ARG, "NMX_TUNE_REDUCE_FORM: 0 = by bucket count, 1 = pair tree, 2 = bit-sliced sums");
+    G.reduce_form = (uint32_t)v;
+  }
   if (const char* t = getenv("NMX_TUNE_TREE_THREADS")) G.tree_threads = (uint32_t)atoi(t);
   if (const char* t = getenv("NMX_TUNE_BIG_SLICE")) G.big_slice = (uint32_t)atoi(t);
   if (const char* t = getenv("NMX_TUNE_BIG_THREADS")) G.big_threads = (uint32_t)atoi(t);
@@ -3216,6 +3222,11 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "prefix_tables") G.prefix_tables = value > 2 ? 2u : (uint32_t)value;
     else if (n == "no_tree_fuse") G.no_tree_fuse = value;
     else if (n == "tree_threads") G.tree_threads = value;
+    else if (n == "no_clean_accum") G.no_clean_accum = value ? 1u : 0u;
+    else if (n == "reduce_form") {
+      require(value <= 2, NMX_E_ARG, "reduce_form: 0 = by bucket count, 1 = pair tree, 2 = bit-sliced sums");
+      G.reduce_form = value;
+    }
     else if (n == "big_slice") G.big_slice = value;
     else if (n == "big_threads") G.big_threads = value;
     else if (n == "hist_grid") G.hist_grid = value;

@@ -253,6 +253,10 @@ template <int FID> struct XYZZ {
   // two call sites of the (fully inlined) addition would make every wave execute it twice.
   template <bool LAT = false> NMX_HD void add_affine(const Affine<FID>& p, bool negate = false) {
     if (p.is_identity()) return;  // msm.rs:130-132
+    add_affine_nonzero<LAT>(p, negate);
+  }
+  // the same for an operand known not to be the identity (rows of a key without identity points)
+  template <bool LAT = false> NMX_HD void add_affine_nonzero(const Affine<FID>& p, bool negate = false) {
 #ifndef NMX_MADD_R2
     add_affine_signed<LAT>(p.x, p.y, negate);
     return;

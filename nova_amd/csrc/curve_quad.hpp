@@ -159,6 +159,7 @@ template <int FID, bool LAT = kLatTail> __device__ __forceinline__ Fp<FID> quad_
 #include "msm_kernels.hpp"
 #include "msm_partition.hpp"
 #include "msm_seg.hpp"
+#include "reduce_bitsliced.hpp"
 namespace nmx {
 
 // coordinate `q` of a raw-limb record (msm_seg.hpp)
@@ -483,6 +484,43 @@ template <int FID, int THREADS> __global__ __launch_bounds__(THREADS) void k_red
     }
     __syncthreads();
   }
+}
+
+// The bucket reduction as bit-sliced sums (reduce_bitsliced.hpp: the plan, the fused body and the single-lane step are shared
+// with the host-side test).  Here: the step with one quad per addition, and the fused kernel -- a quad is a thread group, LDS
+// holds raw limbs, one role only (addition) until the combine at the very end.
+template <int FID> struct BsStepQuadFn {
+  BsStepArgs a;
+  __device__ __forceinline__ void operator()(uint32_t tid) const {
+    const uint32_t q = tid & 3u, item = tid >> 2;
+    if (item >= a.items) return;  // quad-uniform
+    uint32_t gap;
+    const XYZZW* src = bs_step_src(a, item, &gap);
+    quad_store<FID>(a.out[item], q, quad_add<FID>(quad_load<FID>(src[0], q), quad_load<FID>(src[gap], q), q));
+  }
+};
+template <int FID> struct BsQuadPolicy {
+  using V = Fp<FID>;
+  uint32_t* lds_;
+  uint32_t q;
+  __device__ __forceinline__ uint32_t groups() const { return kBsQuads; }
+  __device__ __forceinline__ uint32_t group() const { return threadIdx.x >> 2; }
+  __device__ __forceinline__ uint32_t block() const { return blockIdx.x; }
+  __device__ __forceinline__ bool lead() const { return threadIdx.x == 0; }
+  __device__ __forceinline__ uint32_t* lds() const { return lds_; }
+  __device__ __forceinline__ V load(const XYZZW* p, size_t i) const { return quad_load<FID>(p[i], q); }
+  __device__ __forceinline__ void store(XYZZW* p, size_t i, const V& c) const { quad_store<FID>(p[i], q, c); }
+  __device__ __forceinline__ V lds_load(const uint32_t* b, uint32_t i) const { return lds_load_pt<FID>(b, i, q); }
+  __device__ __forceinline__ void lds_store(uint32_t* b, uint32_t i, const V& c) const { lds_store_pt<FID>(b, i, q, c); }
+  __device__ __forceinline__ V add(const V& x, const V& y) const { return quad_add<FID>(x, y, q); }
+  __device__ __forceinline__ V dbl(const V& x) const { return quad_dbl<FID>(x, q); }
+  __device__ __forceinline__ V ident() const { return V::zero(); }  // zz = 0
+  __device__ __forceinline__ void sync() const { __syncthreads(); }
+};
+template <int FID> __global__ __launch_bounds__(kBsQuads * 4) void k_reduce_bitsliced(BsTreeArgs a) {
+  __shared__ uint32_t lds[(kBsBuf0 + kBsBuf1) * 36];
+  BsQuadPolicy<FID> p{lds, threadIdx.x & 3u};
+  bs_tree_body(p, a);
 }
 
 // ----------------------------------------------------------------------------------------------------

@@ -30,6 +30,7 @@ struct MsmArgs {
   uint32_t no_partition = 0; // 1: generic radix-sort path even where the hand-written partition applies (tests / A-B runs)
   uint32_t seg_min_total = kSegMinTotalAuto;  // segment-balanced accumulate (msm_seg.hpp): automatic, or from this many sorted entries on
   uint32_t seg_min_len = 8;           // shortest segment a lane is given
+  uint32_t accum_clean = 1;           // 0: keys without identity points run the testing instantiation too (option no_clean_accum: A/B)
   uint32_t accum_prefetch = 1;        // gathers in flight ahead of the addition (AccumSegFn PF)
   uint32_t hist_grid = 0;             // blocks of the first-level counting pass (0: as many as the placing pass; tuning)
   uint32_t hist_bs = 0;               // threads per block of the counting pass (0: as the placing pass; it stages nothing, so any multiple of 64 >= the bin count works)
@@ -295,14 +296,18 @@ MsmShape msm_pipeline(BE& be, const MsmArgs& a, uint32_t scalar_bits, XYZZW* wsu
     uint32_t* big_gbase = be.template alloc<uint32_t>(big_cap_s);
     const SegPlan plan{start, end, total_p, counters, heavy_s, big_s, sh.nbuckets, seg_lanes, a.seg_min_len, heavy_above, big_items, big_gbase, big_slice};
     be.mark("accum");
+    auto accum_seg = [&](auto fn) {
+      decltype(fn) f{(const AffineW*)a.bases, vals1, start, end, total_p, bucket_raw, partial_raw, sh.nbuckets,
+                     seg_lanes, a.seg_min_len, plan};
+      be.launch(f, seg_lanes);
+    };
+    const bool clean = a.bases_clean && a.accum_clean;  // no identity row: the instantiation without the per-row test
     if (a.accum_prefetch > 1) {
-      AccumSegFn<FID, 2> f{(const AffineW*)a.bases, vals1, start, end, total_p, bucket_raw, partial_raw, sh.nbuckets,
-                           seg_lanes, a.seg_min_len, plan};
-      be.launch(f, seg_lanes);
+      if (clean) accum_seg(AccumSegFn<FID, 2, true>{});
+      else accum_seg(AccumSegFn<FID, 2, false>{});
     } else {
-      AccumSegFn<FID, 1> f{(const AffineW*)a.bases, vals1, start, end, total_p, bucket_raw, partial_raw, sh.nbuckets,
-                           seg_lanes, a.seg_min_len, plan};
-      be.launch(f, seg_lanes);
+      if (clean) accum_seg(AccumSegFn<FID, 1, true>{});
+      else accum_seg(AccumSegFn<FID, 1, false>{});
     }
     be.mark("fold");
     // big buckets (> 64 pieces) completely; then the heavy ones (> heavy_above) down to heavy_above positions; then

@@ -340,6 +340,8 @@ struct Global {
   std::atomic<uint32_t> big_slice{0};             // env NMX_TUNE_BIG_SLICE / option big_slice: pieces per block of the big-bucket pass (0 = default)
   std::atomic<uint32_t> tree_threads{0};          // env NMX_TUNE_TREE_THREADS / option tree_threads: block size of the fused reduction tree (0 = default, 256 or 512)
   std::atomic<uint32_t> no_tree_fuse{0};          // env NMX_TUNE_NO_TREE_FUSE / option no_tree_fuse: 0 / 2 = fused reduction tree (default), 1 = one launch per reduction level
+  std::atomic<uint32_t> no_clean_accum{0};        // env NMX_TUNE_NO_CLEAN_ACCUM / option no_clean_accum: 1 = keys without identity points also run the segment accumulate that tests every row for the identity (A/B runs)
+  std::atomic<uint32_t> reduce_form{0};           // env NMX_TUNE_REDUCE_FORM / option reduce_form: the bucket reduction: 0 = by bucket count, 1 = pair tree (ReducePairFn / k_reduce_tree), 2 = bit-sliced sums (reduce_bitsliced.hpp)
   std::atomic<uint32_t> hist_grid{0};             // env NMX_TUNE_HIST_GRID / option hist_grid
   std::atomic<uint32_t> hist_bs{0};               // env NMX_TUNE_HIST_BS / option hist_bs: threads per block of k_hist_hi (0: as k_part_hi)
   std::atomic<uint32_t> horner_order{1};          // option horner_order: 1 = tiles of k_horner_scan by start-order ticket, 0 = by block id
@@ -534,12 +536,61 @@ struct DeviceBackend {
     else hipLaunchKernelGGL((k_big_all<FID, 128>), dim3(1024), dim3(128), 0, c.stream, a);
     HIPCHK(hipGetLastError());
   }
+  // Bucket reduction as bit-sliced sums (reduce_bitsliced.hpp): half the additions of the pair tree, no doublings before the end,
+  // one dependent addition per level.  Steps with more additions than one round of blocks holds (256 CUs x 128 quads) take a
+  // launch each, one quad per addition below kQuadBelowItems additions and one lane above; the rest runs fused
+  // (k_reduce_bitsliced), the last launch combines.  Returns null when the pair tree is to run: option reduce_form = 1, by bucket
+  // count under reduce_form = 0, M == 1, or a shape outside bs_plan's index range (a launch of 2^30 additions or 2^31 elements
+  // per array, more than 40 launches): none of the window widths and batch sizes the library runs.
+  // The by-count rule (profiles/r07_reduce/: forms_ab.txt, plan_sweep.txt; reduce stage, pair tree -> bit-sliced):
+  //   128 buckets (c = 8)        52.8 ->  56.2 us   the 7 doublings of the combine outweigh what 7 short levels save: pair tree
+  //   2^14 / 2^15 (c = 15, 16)   116.5 -> 108 us    with at most 64 additions in a block's first level (one wave per SIMD;
+  //                                                 128: 116 us, two waves on a SIMD run one after the other)
+  //   2^16 (c = 17)              149 -> 133-135 us  with 128 (64: 142-157 us -- twice the blocks, or three one-step launches more)
+  //   2^19 (c = 20)              374 -> 345 us      with 128
+  // Bucket counts in between (forced window widths only) take the neighbouring rule; below 2^14 they were not measured and keep
+  // the pair tree.
+  static constexpr uint32_t kBitslicedFromM = 1u << 14, kBitslicedFullBlocksFromM = 1u << 16, kBitslicedWideAbove = 32768;
+  template <int FID> const XYZZW* reduce_bitsliced(const XYZZW* buckets, const MsmShape& sh, const uint32_t* err_src, bool* err_appended) {
+    const uint32_t form = G.reduce_form.load(std::memory_order_relaxed);
+    if (form == 1 || (form == 0 && sh.M < kBitslicedFromM)) return nullptr;
+    BsLaunch plan[kBsMaxLaunches];
+    uint32_t n = 0;
+    // the kernel's LDS always fits (at most 128 additions in a block's first level); what can fail is the 2^31 / 2^30 index range
+    // of a launch and the launch count
+    if (!bs_plan(sh.M, sh.WB, sh.M < kBitslicedFullBlocksFromM ? 64u : 128u, kBitslicedWideAbove, plan, &n)) return nullptr;
+    const XYZZW* in = buckets;
+    const XYZZW* prev_in = nullptr;
+    for (uint32_t i = 0; i < n; i++) {
+      const BsLaunch& l = plan[i];
+      const XYZZW* view = l.view ? prev_in : nullptr;
+      XYZZW* out = l.last ? alloc<XYZZW>(sh.WB + 1)  // + the error word
+                          : alloc<XYZZW>((size_t)bs_out_arrays(l) * bs_out_elems(l));
+      if (!dry) {
+        if (l.wide) {
+          const uint32_t half = l.n_tot / 2, items = (l.n_cont + l.view) * half;
+          const BsStepArgs a{in, view, out, half, l.n_cont, items};
+          if (items < kQuadBelowItems) launch(BsStepQuadFn<FID>{a}, items * 4);
+          else launch(BsStepFn<FID>{a}, items);
+        } else {
+          const BsTreeArgs a{in, view, out, l.n_tot, l.S, l.levels, l.n_cont, l.last, sh.WB, l.last ? err_src : nullptr};
+          hipLaunchKernelGGL((k_reduce_bitsliced<FID>), dim3(l.n_tot / l.S), dim3(kBsQuads * 4), 0, c.stream, a);
+          HIPCHK(hipGetLastError());
+        }
+      }
+      prev_in = in, in = out;
+    }
+    *err_appended = true;
+    return in;
+  }
   // Bucket reduction sum_k (k + 1) B_k per bucket set: the pair tree of ReducePairFn, two dependent quad additions per level.
   // Levels with more inputs than one round of blocks holds (256 CUs x 128 inputs: the kernel runs one 512-thread block per CU
   // at 181 registers) are throughput-bound and keep one launch each; the others run fused, at most seven levels per launch
   // (k_reduce_tree): 16 levels = 1 + 3 launches at c = 17, 15 = 3 at c = 16, 7 = 1 at c = 8.  Returns the WB sums.
   static constexpr uint32_t kTreeThreads = 512, kTreeLevels = 7, kTreeMaxInputs = 256 * 128;
   template <int FID> const XYZZW* reduce_tree(const XYZZW* buckets, const MsmShape& sh, const uint32_t* err_src, bool* err_appended) {
+    if (!dry) (void)launch_gap_ns(c.stream);  // diagnostic only (nmx_stats: NMX_STAT_LAUNCH_GAP_NS), measured once per process
+    if (const XYZZW* sums = reduce_bitsliced<FID>(buckets, sh, err_src, err_appended)) return sums;
     const XYZZW* D = buckets;
     const XYZZW* Y = buckets;
     uint32_t n_in = sh.M, first = 1;  // M == 1 (c == 1): the bucket is the window sum
@@ -550,7 +601,6 @@ struct DeviceBackend {
     // (tail_ab.txt: 2^20 reduce 0.167 -> 0.152 ms, 2^13 0.067 -> 0.055).
     const uint32_t mode = G.no_tree_fuse.load(std::memory_order_relaxed);
     const bool per_level = mode == 1;
-    if (!dry) (void)launch_gap_ns(c.stream);  // diagnostic only (nmx_stats: NMX_STAT_LAUNCH_GAP_NS), measured once per process
     while (n_in > 1 && (per_level || (uint64_t)sh.WB * n_in > kTreeMaxInputs)) {
       const uint32_t half = n_in / 2, pairs = sh.WB * half;
       XYZZW* Do = alloc<XYZZW>(pairs);
