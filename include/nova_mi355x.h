@@ -481,6 +481,53 @@ int nmx_sumcheck_prove_batch_eval(int field, const void* claims, const size_t* n
 int nmx_sumcheck_prove_batched_cubic(int field_id, const void* claim, const void* taus, size_t num_rounds, void* const* As,
                                      void* const* Bs, void* const* Cs, const void* alphas, size_t k, uint32_t flags,
                                      nmx_transcript_fn transcript, void* ctx, uint8_t* out_polys, uint8_t* out_r, uint8_t* out_claims);
+/* nmx_sumcheck_prove_ppsnark == RelaxedR1CSSNARK::prove_helper (src/spartan/ppsnark.rs:886-983), the batched inner sum-check of the
+ * pre-processing SNARK, with its three SumcheckEngine instances behind the boundary: MemorySumcheckInstance (ppsnark.rs:520-670, claims
+ * 0-5, the logUp memory check), InnerBatchedSumcheckInstance (ppsnark.rs:725-786, claims 6-7) and WitnessBoundSumcheck
+ * (ppsnark.rs:293-325, claim 8): ONE sum-check of num_rounds rounds over sixteen tables for nine claims batched by coeffs9.
+ *   field_id    NMX_F_*, as for nmx_sumcheck_prove_batched_cubic (not spelled `field` for the same reason; the refusal of a bad id is
+ *               checked in tests/test_sumcheck_ppsnark_abi.py and tests/test_gpu_sumcheck_ppsnark.py).
+ *   tables      host array of NMX_PPS_TABLES = 16 pointers in the order of the enum below (the reference's fields t_plus_r_row,
+ *               t_plus_r_inv_row, w_plus_r_row, w_plus_r_inv_row, ts_row, the same five for col, L_row, L_col,
+ *               val = val_A + c val_B + c^2 val_C, E, W (padded) and the masked eq table
+ *               MaskedEqPolynomial(eq(r_outer), log2 num_vars).evals(): nmx_eq_evals_from_points, then the first 2^m entries zeroed).
+ *               Every table holds 2^num_rounds elements: HBM-resident with NMX_SCALARS_DEVICE (the intended form), host arrays
+ *               otherwise (uploaded for the call, the host copies left untouched).  The tables are BOUND IN PLACE; their contents
+ *               after the call are unspecified.  All sixteen must be distinct and must not overlap (the reference clones ts_row,
+ *               ts_col, L_row, L_col, E and W for this purpose): an overlap is NMX_E_ARG.
+ *   rhos        num_rounds elements (host): the taus of the memory instance's EqSumCheckInstance;
+ *   r_outer     num_rounds elements (host): the taus of the inner instance's E claim (r_outer_full);
+ *   claims2     two elements: the initial claims 6 (ABC) and 7 (claim_E); the other seven are zero (ppsnark.rs:521-523, :294-296);
+ *   coeffs9     the nine batching coefficients, powers(s, 9) (ppsnark.rs:920-921): the caller squeezes s itself.
+ *               NMX_SCALARS_MONT: everything is Montgomery limbs, otherwise everything is canonical.
+ *   transcript  once per round (ppsnark.rs:930-970) with the 4 coefficients of UniPoly::from_evals_deg3([e0, e - e0, lead, em1]),
+ *               constant term first; its challenge binds all sixteen tables and e becomes poly(r).
+ *   out_polys   num_rounds x 4 x 32 bytes (exactly what the callback received); out_r: num_rounds x 32 bytes;
+ *   out_finals  16 x 32 bytes: every table's value at r, in table order (a superset of the reference's final_claims).  Any output
+ *               may be NULL.
+ * The claims: 0, 1 compute_eval_points_linear (tinv, winv) for row and col (sumcheck.rs:356-379); 2, 4
+ * evaluation_points_cubic_with_three_inputs (tinv, t, ts) and 3, 5 evaluation_points_cubic_with_two_inputs (winv, w) under eq(rhos)
+ * (sumcheck.rs:900-1037); 6 compute_eval_points_cubic (L_row, L_col, val) (sumcheck.rs:416-443); 7
+ * evaluation_points_quadratic_with_one_input (E) under eq(r_outer) (sumcheck.rs:1039-1080); 8 compute_eval_points_quadratic
+ * (masked_eq, W) (sumcheck.rs:384-407).  A zero rhos[j] or r_outer[j] takes the reference's third-sum fallback for the claims under
+ * that eq (sumcheck.rs:1085-1222).
+ * Errors found before a device is leased or anything is written: NULL tables, a NULL entry, a NULL scalar pointer, a null callback, a
+ * bad field_id, a flag other than NMX_SCALARS_MONT / NMX_SCALARS_DEVICE, two tables that overlap: NMX_E_ARG; num_rounds >= 31:
+ * NMX_E_TOO_LARGE; any of the 2 num_rounds + 11 scalars >= p: NMX_E_SCALAR_RANGE.  During the call a challenge >= p is
+ * NMX_E_SCALAR_RANGE and a callback that returns non-zero NMX_E_ARG; on any failure nothing of the call still runs when it returns.
+ * num_rounds == 0: no round, out_finals holds the sixteen single elements.  Thread-safe and re-entrant like the other provers.
+ * A round is four bind + sums passes (memory row, memory col, inner, witness: 18 sums are too many accumulators for one kernel) and a
+ * one-block final sum each into four mailbox slots.  Options honoured: "sc_host_tail" and "sc_poll_us", as for
+ * nmx_sumcheck_prove_batched_cubic; the other sc_* options do NOT affect this call: every pass is launched after its challenge
+ * exists, nothing waits on the device for the host. */
+/* table order of nmx_sumcheck_prove_ppsnark */
+enum { NMX_PPS_T_ROW = 0, NMX_PPS_TINV_ROW, NMX_PPS_W_ROW, NMX_PPS_WINV_ROW, NMX_PPS_TS_ROW,
+       NMX_PPS_T_COL,     NMX_PPS_TINV_COL, NMX_PPS_W_COL, NMX_PPS_WINV_COL, NMX_PPS_TS_COL,
+       NMX_PPS_L_ROW, NMX_PPS_L_COL, NMX_PPS_VAL, NMX_PPS_E, NMX_PPS_W, NMX_PPS_MASKED_EQ, NMX_PPS_TABLES = 16 };
+int nmx_sumcheck_prove_ppsnark(int field_id, size_t num_rounds, void* const* tables /* 16 */, const void* rhos,
+                               const void* r_outer, const void* claims2, const void* coeffs9, uint32_t flags,
+                               nmx_transcript_fn transcript, void* ctx, uint8_t* out_polys, uint8_t* out_r,
+                               uint8_t* out_finals /* 16 x 32 */);
 /* ---- inner-product argument (the evaluation engine of the secondary curve) -----------------------------------------------------
  * InnerProductArgument::prove (src/provider/ipa_pc.rs:174-281), reached through EvaluationEngine::prove (:69-82) -- the evaluation
  * argument of S2 in CompressedSNARK::prove (src/nova/mod.rs:862-881; Grumpkin / Pallas / Vesta engines, src/provider/mod.rs:38-148).

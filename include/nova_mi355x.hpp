@@ -332,6 +332,23 @@ template <int FIELD> struct Sumcheck {
                                            mont ? NMX_SCALARS_MONT : 0u, &detail::round_cb<Transcript>, &tr, p.data(), r.data(), c.data()));
     return detail::unpack(l, 4, 3 * k, p, r, c);
   }
+  // RelaxedR1CSSNARK::prove_helper (ppsnark.rs:886-983): the batched inner sum-check of the pre-processing SNARK over its sixteen tables in
+  // the order NMX_PPS_* (copies: they are bound in place); claims = the sixteen tables at r, in table order
+  template <class Transcript>
+  static SumcheckProof prove_ppsnark(const std::vector<std::vector<Scalar>>& tables, const std::vector<Scalar>& rhos, const std::vector<Scalar>& r_outer,
+                                     const std::array<Scalar, 2>& claims2, const std::array<Scalar, 9>& coeffs, Transcript& tr, bool mont = false) {
+    const size_t l = rhos.size();
+    if (tables.size() != NMX_PPS_TABLES || r_outer.size() != l) throw std::invalid_argument("sixteen tables, one r_outer per rho");
+    std::vector<void*> pt(NMX_PPS_TABLES);
+    for (size_t t = 0; t < NMX_PPS_TABLES; t++) {
+      if (tables[t].size() != (size_t)1 << l) throw std::invalid_argument("tables must hold 2^rhos.len() elements");
+      pt[t] = const_cast<Scalar*>(tables[t].data());
+    }
+    std::vector<uint8_t> p(128 * l + 1), r(32 * l + 1), c(32 * NMX_PPS_TABLES);
+    check(nmx_sumcheck_prove_ppsnark(FIELD, l, pt.data(), rhos.data(), r_outer.data(), claims2.data(), coeffs.data(), mont ? NMX_SCALARS_MONT : 0u,
+                                     &detail::round_cb<Transcript>, &tr, p.data(), r.data(), c.data()));
+    return detail::unpack(l, 4, NMX_PPS_TABLES, p, r, c);
+  }
 };
 }  // namespace spartan
 
@@ -600,6 +617,17 @@ inline Proof prove_batched_cubic(int field, const Scalar& claim, const std::vect
   Proof p{std::vector<uint8_t>(128 * l), std::vector<uint8_t>(32 * l), std::vector<uint8_t>(96 * k)};
   check(nmx_sumcheck_prove_batched_cubic(field, claim.data(), taus.data(), l, As.data(), Bs.data(), Cs.data(), alphas.data(), k, kDev, cb, ctx,
                                          p.polys.data(), p.r.data(), p.claims.data()));
+  return p;
+}
+// prove_helper (ppsnark.rs:886-983) over the sixteen HBM-resident tables of ppsnark's inner sum-check, in the order NMX_PPS_* (no two sharing
+// memory); claims: the sixteen tables at r
+inline Proof prove_ppsnark(int field, const std::vector<void*>& tables, const std::vector<Scalar>& rhos, const std::vector<Scalar>& r_outer,
+                           const std::array<Scalar, 2>& claims2, const std::array<Scalar, 9>& coeffs, nmx_transcript_fn cb, void* ctx) {
+  const size_t l = rhos.size();
+  if (tables.size() != NMX_PPS_TABLES || r_outer.size() != l) throw std::invalid_argument("sixteen tables, one r_outer per rho");
+  Proof p{std::vector<uint8_t>(128 * l), std::vector<uint8_t>(32 * l), std::vector<uint8_t>(32 * NMX_PPS_TABLES)};
+  check(nmx_sumcheck_prove_ppsnark(field, l, tables.data(), rhos.data(), r_outer.data(), claims2.data(), coeffs.data(), kDev, cb, ctx, p.polys.data(),
+                                   p.r.data(), p.claims.data()));
   return p;
 }
 // ck_c.scale(&r) (src/provider/ipa_pc.rs:190-191, pedersen.rs:499-506): one point times one scalar -- a commitment to the empty

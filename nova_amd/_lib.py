@@ -128,6 +128,7 @@ def lib():
     L.nmx_sumcheck_prove_quad_prod.argtypes = [i, vp, sz, vp, vp, u32, TRANSCRIPT_FN, vp, vp, vp, vp]
     L.nmx_sumcheck_prove_batch_eval.argtypes = [i, vp, vp, vp, vp, vp, sz, u32, TRANSCRIPT_FN, vp, vp, vp, vp]
     L.nmx_sumcheck_prove_batched_cubic.argtypes = [i, vp, vp, sz, vp, vp, vp, vp, sz, u32, TRANSCRIPT_FN, vp, vp, vp, vp]
+    L.nmx_sumcheck_prove_ppsnark.argtypes = [i, sz, vp, vp, vp, vp, vp, u32, TRANSCRIPT_FN, vp, vp, vp, vp]
     L.nmx_ipa_prove.argtypes = [u64, vp, vp, vp, sz, u32, IPA_TRANSCRIPT_FN, vp, vp, vp, vp, vp]
     L.nmx_ipa_verify.argtypes = [u64, vp, vp, i, vp, vp, sz, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.nmx_set_profiling.argtypes = [i]

@@ -2830,6 +2830,47 @@ int nmx_sumcheck_prove_batched_cubic(int field_id, const void* claim, const void
     fv_sumcheck_prove_batched_cubic(*L.c, field_id, claim, taus, num_rounds, As, Bs, Cs, alphas, k, flags, transcript, ctx, out_polys, out_r, out_claims);
   });
 }
+// RelaxedR1CSSNARK::prove_helper (ppsnark.rs:886-983; sumcheck_ppsnark.hpp).  As above, everything that can be refused is refused
+// before a device is leased: the sixteen tables are bound in place.
+int nmx_sumcheck_prove_ppsnark(int field_id, size_t num_rounds, void* const* tables, const void* rhos, const void* r_outer, const void* claims2,
+                               const void* coeffs9, uint32_t flags, nmx_transcript_fn transcript, void* ctx, uint8_t* out_polys, uint8_t* out_r,
+                               uint8_t* out_finals) {
+  return guarded([&] {
+    check_sc_args(field_id, num_rounds, flags, transcript);
+    require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE)) == 0, NMX_E_ARG, "prove_ppsnark: unknown flag");
+    require(tables && (rhos || num_rounds == 0) && (r_outer || num_rounds == 0) && claims2 && coeffs9, NMX_E_ARG, "null argument");
+    const size_t n = (size_t)1 << num_rounds, bytes = n * 32;
+    std::vector<std::pair<uintptr_t, uintptr_t>> span;
+    for (size_t t = 0; t < NMX_PPS_TABLES; t++) {
+      require(tables[t] != nullptr, NMX_E_ARG, "prove_ppsnark: null table");
+      span.emplace_back((uintptr_t)tables[t], (uintptr_t)tables[t] + bytes);
+    }
+    std::sort(span.begin(), span.end());
+    for (size_t i = 1; i < span.size(); i++)
+      require(span[i - 1].second <= span[i].first, NMX_E_ARG, "prove_ppsnark: two tables overlap (they are bound in place)");
+    with_field(field_id, [&](auto F) {
+      using Field = Fp<decltype(F)::value>;
+      auto lt_p = [](const void* p, size_t i) {
+        uint32_t w[8];
+        memcpy(w, (const uint8_t*)p + 32 * i, 32);
+        return Field::words_lt_p(w);
+      };
+      bool ok = lt_p(claims2, 0) && lt_p(claims2, 1);
+      for (size_t i = 0; i < num_rounds; i++) ok = ok && lt_p(rhos, i) && lt_p(r_outer, i);
+      for (size_t i = 0; i < 9; i++) ok = ok && lt_p(coeffs9, i);
+      require(ok, NMX_E_SCALAR_RANGE, "prove_ppsnark: rho / r_outer / claim / coefficient >= field modulus");
+    });
+    CtxLease L;
+    ScStaged st;
+    std::vector<void*> staged;
+    if (!(flags & NMX_SCALARS_DEVICE)) {
+      for (size_t t = 0; t < NMX_PPS_TABLES; t++) staged.push_back(st.up(*L.c, tables[t], n));
+      tables = staged.data();
+      flags |= NMX_SCALARS_DEVICE;
+    }
+    fv_sumcheck_prove_ppsnark(*L.c, field_id, num_rounds, tables, rhos, r_outer, claims2, coeffs9, flags, transcript, ctx, out_polys, out_r, out_finals);
+  });
+}
 
 // Device state of one call that has to outlive the MSMs the call runs (they re-carve the context's arena): the context's aux buffer
 // up to kAuxMax bytes, an allocation of the call's own above that; carved front to back.  `ev`, if the call creates it, goes with it.

@@ -852,6 +852,9 @@ void fv_sumcheck_prove_batch(Ctx&, int field, const uint8_t* claims, const size_
 void fv_sumcheck_prove_batched_cubic(Ctx&, int field, const void* claim, const void* taus, size_t num_rounds, void* const* As, void* const* Bs,
                                      void* const* Cs, const void* alphas, size_t k, uint32_t flags, TranscriptFn cb, void* cb_ctx,
                                      uint8_t* out_polys, uint8_t* out_r, uint8_t* out_claims);  // sumcheck_batched.hpp
+void fv_sumcheck_prove_ppsnark(Ctx&, int field, size_t num_rounds, void* const* tables, const void* rhos, const void* r_outer,
+                               const void* claims2, const void* coeffs9, uint32_t flags, TranscriptFn cb, void* cb_ctx, uint8_t* out_polys,
+                               uint8_t* out_r, uint8_t* out_finals);  // sumcheck_ppsnark.hpp
 
 const CurveOps& curve_ops_bn254_g1();
 const CurveOps& curve_ops_grumpkin();

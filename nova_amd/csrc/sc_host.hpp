@@ -9,6 +9,9 @@
 //   fallback_eval_inf_three_inputs / _one_input (tau = 0)                    sumcheck.rs:1085-1136, 1185-1222
 //   compute_eval_points_quad_prod                                            sumcheck.rs:163-186
 //   evaluation_points_batched_cubic / fallback_eval_inf_batched_cubic        sumcheck.rs:749-894
+//   compute_eval_points_linear / _quadratic / _cubic                         sumcheck.rs:356-443
+//   evaluation_points_cubic_with_two_inputs / fallback_eval_inf_two_inputs   sumcheck.rs:972-1037, 1138-1181
+//   RelaxedR1CSSNARK::prove_helper and its three SumcheckEngine instances    ppsnark.rs:886-983, 293-325, 520-670, 725-786
 //   UniPoly::from_evals_deg2 / _deg3 / evaluate                              polys/univariate.rs:90-113, 140-149
 //   SumcheckProof::update_claim                                              sumcheck.rs:68-75
 //   MultilinearPolynomial::bind_poly_var_top                                 polys/multilinear.rs:65-84
@@ -80,6 +83,12 @@ template <int FID> struct ScAlg {
     const H e1 = claim - e0;
     const H a1 = (e1 - em1) * two_inv(), a2 = (e1 + em1) * two_inv() - e0;
     return e0 + r * (a1 + r * a2);
+  }
+  // the same with a cubic coefficient: evals [e0, c3, em1] as the reference has it
+  static H update_claim3(const H& claim, const H& e0, const H& c3, const H& em1, const H& r) {
+    const H e1 = claim - e0;
+    const H a1 = (e1 - em1) * two_inv() - c3, a2 = (e1 + em1) * two_inv() - e0;
+    return e0 + r * (a1 + r * (a2 + r * c3));
   }
   static H pow2(uint32_t e) { return H::pow2(e); }
 
@@ -304,6 +313,136 @@ void sc_tail_rounds_batched(const ScAlg<FID>& alg, typename ScAlg<FID>::Eq* eq, 
     claim = ScAlg<FID>::poly_eval(co, 4, r);
     for (size_t i = 0; i < k; i++) ScAlg<FID>::bind_top(A[i], r), ScAlg<FID>::bind_top(B[i], r), ScAlg<FID>::bind_top(C[i], r);
     eq->bound(r);
+  }
+}
+
+// ppsnark's batched inner sum-check (RelaxedR1CSSNARK::prove_helper, ppsnark.rs:886-983): nine claims over sixteen tables, batched by
+// the caller's coefficients.  The scalar state of one proof and the O(1) algebra of a round; the sums come from the device
+// (sumcheck_ppsnark.hpp) or from host_sums below.  Table order: include/nova_mi355x.h NMX_PPS_*.
+//   claims 0, 1  compute_eval_points_linear (tinv, winv), row / col: [D(0), 0, D(-1)]; D is linear, so D(-1) = 2 D(0) - D(1) with D(1)
+//                the plain sum over the high halves
+//   claims 2, 4  evaluation_points_cubic_with_three_inputs (tinv, t, ts) under eq(rhos)   -> Eq::derive, eq[0] / eq[2]
+//   claims 3, 5  evaluation_points_cubic_with_two_inputs (winv, w) under eq(rhos)         -> Eq::derive, eq[1] / eq[3]
+//   claim 6      compute_eval_points_cubic (L_row, L_col, val)
+//   claim 7      evaluation_points_quadratic_with_one_input (E) under eq(r_outer)         -> Eq::derive (deg1), eq[4]
+//   claim 8      compute_eval_points_quadratic (masked_eq, W): [e(0), 0, e(-1)]
+// The reference keeps a running claim per derived claim (update_claim, sumcheck.rs:68-75, ppsnark.rs:631-635, :764-766); Eq tracks the
+// inner claim T of its instance instead (see Eq above: the same field elements), so each derived claim has an Eq of its own.
+template <int FID> struct ScPps {
+  using H = typename ScAlg<FID>::H;
+  using Eq = typename ScAlg<FID>::Eq;
+  static constexpr uint32_t kTables = 16, kClaims = 9, kDerived = 5;
+  Eq eq[kDerived];      // claims 2, 3, 4, 5 (taus = rhos) and 7 (taus = r_outer)
+  H coeff[kClaims], e;  // the batching coefficients; the joint claim
+  H claim_E;            // claim 7's initial claim: the inner claim of eq[4]'s first round
+  mutable H ev[kClaims][3];  // the nine claims' [p(0), cubic coefficient, p(-1)] of the round round_poly last ran for
+  struct Sums {
+    H lin[2][2];     // [row / col]: D(0), D(1) = sum (tinv - winv) over the low / the high halves
+    H mem[2][2][2];  // [row / col][T / W]: t(0), t(inf)
+    H cub[3];        // sum a b c, sum da db dc, sum a(-1) b(-1) c(-1)
+    H e_t0;          // sum eq(r_outer) E over the low halves
+    H wit[2];        // sum A B, sum A(-1) B(-1)
+  };
+  void init(const ScAlg<FID>& a, const void* rhos, const void* r_outer, const void* claims2, const void* coeffs9, uint32_t l) {
+    for (uint32_t i = 0; i < 4; i++) eq[i].init(a, (const uint8_t*)rhos, l);
+    eq[4].init(a, (const uint8_t*)r_outer, l);
+    for (uint32_t i = 0; i < kClaims; i++) coeff[i] = a.in((const uint8_t*)coeffs9 + 32 * i);
+    const H claim_ABC = a.in(claims2);
+    claim_E = a.in((const uint8_t*)claims2 + 32);
+    e = coeff[6] * claim_ABC + coeff[7] * claim_E;  // the other seven initial claims are zero (ppsnark.rs:521-523, :294-296, :924)
+  }
+  // the round polynomial (ppsnark.rs:930-954).  t1(i): t(1) of derived claim i (0..3: row T, row W, col T, col W; 4: E) -- its t(0)
+  // sum over the HIGH halves; asked for only when that claim's tau is zero (the third sum of the fallback_eval_inf_* paths)
+  template <class T1> void round_poly(const Sums& s, T1&& t1, H co[4]) const {
+    for (uint32_t g = 0; g < 2; g++) {
+      ev[g][0] = s.lin[g][0], ev[g][1] = H::zero(), ev[g][2] = s.lin[g][0].dbl() - s.lin[g][1];
+      for (uint32_t w = 0; w < 2; w++) {
+        const H &t0 = s.mem[g][w][0], &tinf = s.mem[g][w][1];
+        const uint32_t d = 2 * g + w;
+        eq[d].derive(t0, tinf, H::zero(), false, ev[2 + d][0], ev[2 + d][1], ev[2 + d][2], [&] { return tinf.dbl() + t0.dbl() - t1(d); });
+      }
+    }
+    ev[6][0] = s.cub[0], ev[6][1] = s.cub[1], ev[6][2] = s.cub[2];
+    eq[4].derive(s.e_t0, H::zero(), claim_E, true, ev[7][0], ev[7][1], ev[7][2], [&] { return s.e_t0.dbl() - t1(4); });
+    ev[8][0] = s.wit[0], ev[8][1] = H::zero(), ev[8][2] = s.wit[1];
+    H c0 = H::zero(), lead = H::zero(), cm1 = H::zero();
+    for (uint32_t i = 0; i < kClaims; i++) c0 = c0 + ev[i][0] * coeff[i], lead = lead + ev[i][1] * coeff[i], cm1 = cm1 + ev[i][2] * coeff[i];
+    ScAlg<FID>::from_evals_deg3(c0, e, lead, cm1, co);
+  }
+  // ppsnark.rs:631-653, :764-778 (the scalars' part).  Eq's inner claim T stands for the reference's running claim as long as
+  // running = eval_eq_left T, which every round keeps whose s(1) came from the claim.  A round with tau = 0 computes s(1) = 0 instead
+  // while update_claim still takes e1 = claim - e0: the same number when the claim is true, another one when it is not (an instance
+  // that no verifier accepts).  To give the reference's output there too, such a round restates update_claim on the running claim
+  // and re-bases T on it -- one inversion, in fall-back rounds only.  (eval_eq_left = 0 afterwards: every later part of this claim
+  // is zero whatever T is.)
+  void bound(const H co[4], const H& r) {
+    e = ScAlg<FID>::poly_eval(co, 4, r);
+    for (uint32_t d = 0; d < kDerived; d++) {
+      Eq& q = eq[d];
+      const bool fallback = q.l1p_zero;  // of the round derive() just ran for
+      H running = H::zero();
+      if (fallback) {
+        const H* x = ev[d < 4 ? 2 + d : 7];
+        const H claim = q.round == 1 ? (d < 4 ? H::zero() : claim_E) : q.eval_eq_left * q.T;
+        running = ScAlg<FID>::update_claim3(claim, x[0], x[1], x[2], r);
+      }
+      q.bound(r);
+      if (fallback && !q.eval_eq_left.is_zero()) q.T = running * q.eval_eq_left.inv();
+    }
+  }
+  // the sums of a round over host tables (T[i]: table i, all of one even length); facR / facO: Eq::factors of eq[0] / eq[4]
+  static Sums host_sums(const std::vector<H>* T, const std::vector<H>& facR, const std::vector<H>& facO) {
+    const size_t h = T[0].size() / 2;
+    Sums s;
+    for (uint32_t g = 0; g < 2; g++) {
+      const std::vector<H>&t = T[5 * g], &tinv = T[5 * g + 1], &w = T[5 * g + 2], &winv = T[5 * g + 3], &ts = T[5 * g + 4];
+      H d0 = H::zero(), d1 = H::zero(), a0 = H::zero(), a1 = H::zero(), b0 = H::zero(), b1 = H::zero();
+      for (size_t i = 0; i < h; i++) {
+        d0 = d0 + (tinv[i] - winv[i]), d1 = d1 + (tinv[i + h] - winv[i + h]);
+        a0 = a0 + (tinv[i] * t[i] - ts[i]) * facR[i], a1 = a1 + (tinv[i + h] - tinv[i]) * (t[i + h] - t[i]) * facR[i];
+        b0 = b0 + (winv[i] * w[i] - H::one()) * facR[i], b1 = b1 + (winv[i + h] - winv[i]) * (w[i + h] - w[i]) * facR[i];
+      }
+      s.lin[g][0] = d0, s.lin[g][1] = d1, s.mem[g][0][0] = a0, s.mem[g][0][1] = a1, s.mem[g][1][0] = b0, s.mem[g][1][1] = b1;
+    }
+    const std::vector<H>&A = T[10], &B = T[11], &C = T[12], &E = T[13], &W = T[14], &M = T[15];
+    H c0 = H::zero(), c1 = H::zero(), c2 = H::zero(), e0 = H::zero(), w0 = H::zero(), w1 = H::zero();
+    for (size_t i = 0; i < h; i++) {
+      const H da = A[i + h] - A[i], db = B[i + h] - B[i], dc = C[i + h] - C[i];
+      c0 = c0 + A[i] * B[i] * C[i], c1 = c1 + da * db * dc, c2 = c2 + (A[i] - da) * (B[i] - db) * (C[i] - dc);
+      e0 = e0 + E[i] * facO[i];
+      w0 = w0 + M[i] * W[i], w1 = w1 + (M[i].dbl() - M[i + h]) * (W[i].dbl() - W[i + h]);
+    }
+    s.cub[0] = c0, s.cub[1] = c1, s.cub[2] = c2, s.e_t0 = e0, s.wit[0] = w0, s.wit[1] = w1;
+    return s;
+  }
+  // t(1) of derived claim d over host tables: the claim's t(0) summand at the high halves
+  static H host_t1(uint32_t d, const std::vector<H>* T, const std::vector<H>& facR, const std::vector<H>& facO) {
+    const size_t h = T[0].size() / 2;
+    H s = H::zero();
+    if (d == 4) {
+      for (size_t i = 0; i < h; i++) s = s + T[13][i + h] * facO[i];
+      return s;
+    }
+    const uint32_t g = d / 2;
+    const std::vector<H>&inv = T[5 * g + (d & 1 ? 3 : 1)], &x = T[5 * g + (d & 1 ? 2 : 0)], &ts = T[5 * g + 4];
+    for (size_t i = 0; i < h; i++) s = s + (inv[i + h] * x[i + h] - (d & 1 ? H::one() : ts[i + h])) * facR[i];
+    return s;
+  }
+};
+
+// The rounds j0 .. l of prove_helper (ppsnark.rs:930-970) over the sixteen HOST tables of the current length.  On return every table
+// holds one element: its value at r.
+template <int FID>
+void sc_tail_rounds_ppsnark(const ScAlg<FID>& alg, ScPps<FID>& st, uint32_t l, uint32_t j0, std::vector<typename ScAlg<FID>::H>* T,
+                            TranscriptFn cb, void* cb_ctx, uint8_t* out_polys, uint8_t* out_r) {
+  using H = typename ScAlg<FID>::H;
+  for (uint32_t j = j0; j <= l; j++) {
+    const std::vector<H> facR = st.eq[0].factors(j), facO = st.eq[4].factors(j);
+    H co[4];
+    st.round_poly(ScPps<FID>::host_sums(T, facR, facO), [&](uint32_t d) { return ScPps<FID>::host_t1(d, T, facR, facO); }, co);
+    const H r = alg.ask(cb, cb_ctx, co, 4, out_polys ? out_polys + 128 * (size_t)(j - 1) : nullptr, out_r ? out_r + 32 * (size_t)(j - 1) : nullptr);
+    st.bound(co, r);
+    for (uint32_t t = 0; t < ScPps<FID>::kTables; t++) ScAlg<FID>::bind_top(T[t], r);
   }
 }
 

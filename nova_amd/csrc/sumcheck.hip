@@ -836,5 +836,6 @@ void fv_eq_sums(Ctx& c, int field, int mode, const void* A, const void* B, const
 
 #include "sumcheck_prove.hpp"
 #include "sumcheck_batched.hpp"
+#include "sumcheck_ppsnark.hpp"
 #include "ipa.hpp"
 #include "ipa_verify.hpp"

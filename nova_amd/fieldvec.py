@@ -580,6 +580,36 @@ def sumcheck_prove_batched_cubic(field, claim, taus, As, Bs, Cs, alphas, transcr
     return _rows(polys, nr, 4), [x[0] for x in _rows(r, nr, 1)], _rows(out, k, 3)
 
 
+PPS_TABLES = ("t_plus_r_row", "t_plus_r_inv_row", "w_plus_r_row", "w_plus_r_inv_row", "ts_row", "t_plus_r_col", "t_plus_r_inv_col", "w_plus_r_col",
+              "w_plus_r_inv_col", "ts_col", "L_row", "L_col", "val", "E", "W", "masked_eq")    # include/nova_mi355x.h NMX_PPS_*
+
+
+def sumcheck_prove_ppsnark(field, tables, rhos, r_outer, claims2, coeffs, transcript, mont=False, ctx=None):
+    """RelaxedR1CSSNARK::prove_helper (src/spartan/ppsnark.rs:886-983): ppsnark's batched inner sum-check, nine claims over the sixteen
+    tables of PPS_TABLES (that order), each of 2^len(rhos) elements -- CUDA tensors, bound IN PLACE (contents unspecified afterwards), or
+    host arrays (uploaded for the call, left untouched); no two tables may share memory.  rhos, r_outer (len(rhos) elements each),
+    claims2 (claim_ABC, claim_E) and coeffs (nine) are host.  Returns (round polynomials [rounds][4], challenges [rounds], the sixteen
+    tables' values at r) as 32-byte strings."""
+    import ctypes
+    assert len(tables) == len(PPS_TABLES), "sixteen tables, in the order of PPS_TABLES"
+    rh, ro = _host_u8(rhos, 32), _host_u8(r_outer, 32)
+    nr = rh.size // 32
+    assert ro.size // 32 == nr, "one r_outer per rho"
+    parts = [_vec(x) for x in tables]
+    dev = parts[0][2]
+    assert all(pt[2] == dev for pt in parts), "all tables in HBM or all on the host"
+    assert all(pt[1] == (1 << nr) for pt in parts), "every table holds 2^len(rhos) elements"
+    ptrs = (ctypes.c_void_p * len(parts))(*[pt[0] for pt in parts])
+    c2 = _host_u8(b"".join(claims2) if isinstance(claims2, (list, tuple)) else claims2, 32)
+    co = _host_u8(b"".join(coeffs) if isinstance(coeffs, (list, tuple)) else coeffs, 32)
+    assert c2.size == 64 and co.size == 9 * 32, "two claims, nine coefficients"
+    polys, r, fin = np.zeros(128 * max(nr, 1), np.uint8), np.zeros(32 * max(nr, 1), np.uint8), np.zeros(32 * len(parts), np.uint8)
+    cb = as_transcript(transcript)
+    _check(L.lib().nmx_sumcheck_prove_ppsnark(field, nr, ptrs, rh.ctypes.data if nr else None, ro.ctypes.data if nr else None, c2.ctypes.data,
+                                             co.ctypes.data, _flags(dev, mont), cb, ctx, polys.ctypes.data, r.ctypes.data, fin.ctypes.data))
+    return _rows(polys, nr, 4), [x[0] for x in _rows(r, nr, 1)], [x[0] for x in _rows(fin, len(parts), 1)]
+
+
 # ---- R1CSShape::is_sat / is_sat_relaxed as one call (nmx_r1cs_is_sat; src/r1cs/mod.rs:474-574) -----------------------------------
 class SatResult:
     """Answer of r1cs_is_sat / r1cs_is_sat_relaxed.  `ok` is the reference's Ok(()); eq_ok false is its UnSat "... is unsatisfiable",
