@@ -528,6 +528,53 @@ int nmx_sumcheck_prove_ppsnark(int field_id, size_t num_rounds, void* const* tab
                                const void* r_outer, const void* claims2, const void* coeffs9, uint32_t flags,
                                nmx_transcript_fn transcript, void* ctx, uint8_t* out_polys, uint8_t* out_r,
                                uint8_t* out_finals /* 16 x 32 */);
+/* ---- ppsnark's lookup gather and fused logUp oracles: ten of the sixteen tables above, produced in HBM ------------------------------
+ * nmx_field_gather: out[i] = mem[addr[i]], i < n -- R1CSShapeSparkRepr::evaluation_oracles (src/spartan/ppsnark.rs:220-253, called from
+ * prove at :1154): L_row[i] = eq(r_outer_full)[row[i]] and L_col[i] = z[col[i]].
+ *   field_id   NMX_F_* (not spelled `field`, as for the sum-check provers; the refusal of a bad id is checked in
+ *              tests/test_ppsnark_oracles_abi.py and tests/test_gpu_ppsnark_oracles.py).
+ *   mem        n_mem elements; their 32 bytes are copied as they are.
+ *   addr       n FIELD ELEMENTS whose integer values are the addresses -- the form the reference keeps row / col in as committed
+ *              polynomials (ppsnark.rs:180-181) and the form nmx_ppsnark_mem_oracles takes them in.  With NMX_SCALARS_MONT the words are
+ *              Montgomery limbs (the kernel takes them out of that form with one product); otherwise canonical integers.
+ *   flags      NMX_SCALARS_MONT; NMX_SCALARS_DEVICE: mem, addr and out are in HBM, otherwise host arrays staged for the call.  Any other
+ *              flag is NMX_E_ARG -- NMX_ASYNC too: the call reads a device error word back and is synchronous.
+ * Errors found before a device is touched, with nothing written: a NULL pointer or n_mem == 0 with n > 0, a bad field_id, an unknown flag,
+ * out overlapping mem or addr: NMX_E_ARG; n or n_mem >= 2^32: NMX_E_TOO_LARGE.  Found on the device: an address whose value is not
+ * below n_mem (the reference panics on the index) -- non-zero high words, and with NMX_SCALARS_MONT words at or above p, included -- is
+ * NMX_E_ARG: the kernel reads nothing through such an address, raises one device word, and the host reads that word after the launch.
+ * The contents of out are then unspecified (as for nmx_field_batch_invert's failure); nothing of the call still runs when it returns.
+ * n == 0: NMX_OK, no launch.  Thread-safe, and ordered behind the calling thread's NMX_ASYNC calls like every synchronous call. */
+int nmx_field_gather(int field_id, const void* mem, size_t n_mem, const void* addr, size_t n,
+                     uint32_t flags, void* out /* n */);
+/* nmx_ppsnark_mem_oracles == MemorySumcheckInstance::compute_oracles (src/spartan/ppsnark.rs:371-489, called from prove at :1197) without
+ * its four commitments (those are nmx_commit / nmx_msm_batch_handle over the outputs), for k memories of n elements in ONE call -- the
+ * reference has row and col, k = 2, joined under rayon::join.  For memory m and i < n:
+ *     out_t_plus_r[m][i]     = mem[m][i] * gamma + i + r                 (the hash of the table entry, ppsnark.rs:389-396; + r :424-428)
+ *     out_w_plus_r[m][i]     = L[m][i] * gamma + addr[m][i] + r          (the hash of the lookup, ppsnark.rs:397-401)
+ *     out_t_plus_r_inv[m][i] = ts[m][i] / out_t_plus_r[m][i]             (batch_invert, ppsnark.rs:430, then the product by ts, :439-441)
+ *     out_w_plus_r_inv[m][i] = 1 / out_w_plus_r[m][i]
+ * i enters as a field element in the vectors' form.  All outputs are canonical (< p) in the inputs' form; the four outputs of memory m
+ * are exactly tables NMX_PPS_T_ROW + 5 m, NMX_PPS_W_ROW + 5 m, NMX_PPS_TINV_ROW + 5 m and NMX_PPS_WINV_ROW + 5 m of
+ * nmx_sumcheck_prove_ppsnark.
+ *   field_id   NMX_F_*, as above.
+ *   k, n       1 <= k <= 8 memories of n >= 1 elements each.
+ *   mem, addr, L, ts, out_*   host arrays of k pointers, one vector of n elements each.  Inputs may alias one another.
+ *   gamma, r   one element each, always host pointers.
+ *   flags      NMX_SCALARS_MONT: vectors, gamma and r are Montgomery limbs, otherwise canonical.  NMX_SCALARS_DEVICE: every vector,
+ *              inputs and outputs, is in HBM; otherwise host arrays staged for the call.  Any other flag is NMX_E_ARG -- NMX_ASYNC
+ *              too: the top of the inversion runs on the host.
+ * Errors found before a device is touched, with nothing written: a NULL array or entry, a NULL gamma or r, k outside 1 .. 8, n == 0, a
+ * bad field_id, an unknown flag, any output overlapping any input or another output: NMX_E_ARG; 2 k n >= 2^32: NMX_E_TOO_LARGE; gamma
+ * or r at or above p: NMX_E_SCALAR_RANGE.  Some T + r or W + r zero: NMX_E_ZERO (the reference's batch_invert(..)? is
+ * NovaError::InternalError, ppsnark.rs:430); the outputs are then unspecified and nothing of the call still runs when it returns.
+ * Vector words are taken to be below p.  Montgomery's trick over the 2 k n values as one batch: level 0 fused with the hashing and the
+ * product by ts, the levels above and the host top those of nmx_field_batch_invert (nova_amd/csrc/ppsnark_oracles.hpp). */
+int nmx_ppsnark_mem_oracles(int field_id, size_t k, size_t n,
+                            const void* const* mem, const void* const* addr, const void* const* L, const void* const* ts,
+                            const void* gamma, const void* r, uint32_t flags,
+                            void* const* out_t_plus_r, void* const* out_w_plus_r,
+                            void* const* out_t_plus_r_inv, void* const* out_w_plus_r_inv);
 /* ---- inner-product argument (the evaluation engine of the secondary curve) -----------------------------------------------------
  * InnerProductArgument::prove (src/provider/ipa_pc.rs:174-281), reached through EvaluationEngine::prove (:69-82) -- the evaluation
  * argument of S2 in CompressedSNARK::prove (src/nova/mod.rs:862-881; Grumpkin / Pallas / Vesta engines, src/provider/mod.rs:38-148).

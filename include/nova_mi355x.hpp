@@ -585,6 +585,23 @@ inline Scalar mercury_quot_f(int field, const void* f, size_t n, const void* q, 
   // one-coefficient polynomial {out[0]} evaluated at 0 is out[0]
   return poly_eval_multi(field, {out}, {1}, {Scalar{}})[0];
 }
+// ppsnark's evaluation_oracles (ppsnark.rs:220-253): out[i] = mem[addr[i]], addr n field elements whose values are the addresses; all in HBM
+inline void gather(int field, const void* mem, size_t n_mem, const void* addr, size_t n, void* out, bool mont = false) {
+  check(nmx_field_gather(field, mem, n_mem, addr, n, kDev | (mont ? NMX_SCALARS_MONT : 0u), out));
+}
+// ppsnark's compute_oracles (ppsnark.rs:371-489) without its commitments, every memory in one call: mem, addr, L, ts and the four outputs
+// hold one HBM pointer per memory, n elements each.  Throws Error with code NMX_E_ZERO when some T + r or W + r is zero.
+inline void ppsnark_mem_oracles(int field, size_t n, const std::vector<const void*>& mem, const std::vector<const void*>& addr,
+                                const std::vector<const void*>& L, const std::vector<const void*>& ts, const Scalar& gamma, const Scalar& r,
+                                const std::vector<void*>& t_plus_r, const std::vector<void*>& w_plus_r, const std::vector<void*>& t_plus_r_inv,
+                                const std::vector<void*>& w_plus_r_inv, bool mont = false) {
+  const size_t k = mem.size();
+  if (addr.size() != k || L.size() != k || ts.size() != k || t_plus_r.size() != k || w_plus_r.size() != k || t_plus_r_inv.size() != k ||
+      w_plus_r_inv.size() != k)
+    throw std::invalid_argument("ppsnark_mem_oracles: one pointer per memory in every array");
+  check(nmx_ppsnark_mem_oracles(field, k, n, mem.data(), addr.data(), L.data(), ts.data(), gamma.data(), r.data(),
+                                kDev | (mont ? NMX_SCALARS_MONT : 0u), t_plus_r.data(), w_plus_r.data(), t_plus_r_inv.data(), w_plus_r_inv.data()));
+}
 // the sum-check provers over HBM-resident tables (bound in place); `cb` / `ctx`: nmx_transcript_fn and its state
 struct Proof {
   std::vector<uint8_t> polys, r, claims;

@@ -2872,6 +2872,66 @@ int nmx_sumcheck_prove_ppsnark(int field_id, size_t num_rounds, void* const* tab
   });
 }
 
+// ---- ppsnark's lookup gather and fused logUp oracles (ppsnark_oracles.hpp; src/spartan/ppsnark.rs:220-253 and :371-489) -----------------------
+// Everything that can be refused is refused before a device is leased: a refused call needs no device, launches nothing, writes nothing.
+int nmx_field_gather(int field_id, const void* mem, size_t n_mem, const void* addr, size_t n, uint32_t flags, void* out) {
+  return guarded([&] {
+    require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE)) == 0, NMX_E_ARG,
+            "nmx_field_gather: only NMX_SCALARS_MONT and NMX_SCALARS_DEVICE apply (the call is synchronous)");
+    with_field(field_id, [](auto) {});
+    require((mem && addr && out) || n == 0, NMX_E_ARG, "null argument");
+    require(n_mem > 0 || n == 0, NMX_E_ARG, "nmx_field_gather: n_mem == 0 with n > 0");
+    require(n < (1ull << 32) && n_mem < (1ull << 32), NMX_E_TOO_LARGE, "nmx_field_gather: n and n_mem must stay below 2^32");
+    require(!mercury_overlap(out, n, mem, n_mem) && !mercury_overlap(out, n, addr, n), NMX_E_ARG, "nmx_field_gather: out overlaps mem or addr");
+    if (n == 0) return;
+    CtxLease L;
+    if (!fv_gather(*L.c, field_id, mem, n_mem, addr, n, flags, out))
+      throw Fail{NMX_E_ARG, "nmx_field_gather: an address is not below n_mem (the reference panics on the index)"};
+  });
+}
+int nmx_ppsnark_mem_oracles(int field_id, size_t k, size_t n, const void* const* mem, const void* const* addr, const void* const* L_,
+                            const void* const* ts, const void* gamma, const void* r, uint32_t flags, void* const* out_t_plus_r,
+                            void* const* out_w_plus_r, void* const* out_t_plus_r_inv, void* const* out_w_plus_r_inv) {
+  return guarded([&] {
+    require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE)) == 0, NMX_E_ARG,
+            "nmx_ppsnark_mem_oracles: only NMX_SCALARS_MONT and NMX_SCALARS_DEVICE apply (the top of the inversion runs on the host)");
+    with_field(field_id, [](auto) {});
+    require(mem && addr && L_ && ts && gamma && r && out_t_plus_r && out_w_plus_r && out_t_plus_r_inv && out_w_plus_r_inv, NMX_E_ARG, "null argument");
+    require(k >= 1 && k <= 8, NMX_E_ARG, "nmx_ppsnark_mem_oracles: k must be 1 .. 8");
+    require(n >= 1, NMX_E_ARG, "nmx_ppsnark_mem_oracles: n must be at least 1");
+    require(n < (1ull << 32) && 2 * (uint64_t)k * (uint64_t)n < (1ull << 32), NMX_E_TOO_LARGE, "nmx_ppsnark_mem_oracles: 2 k n must stay below 2^32");
+    std::vector<std::pair<uintptr_t, uintptr_t>> ins, outs;
+    for (size_t m = 0; m < k; m++) {
+      for (const void* p : {mem[m], addr[m], L_[m], ts[m]}) {
+        require(p != nullptr, NMX_E_ARG, "nmx_ppsnark_mem_oracles: null vector");
+        ins.emplace_back((uintptr_t)p, (uintptr_t)p + n * 32);
+      }
+      for (void* p : {out_t_plus_r[m], out_w_plus_r[m], out_t_plus_r_inv[m], out_w_plus_r_inv[m]}) {
+        require(p != nullptr, NMX_E_ARG, "nmx_ppsnark_mem_oracles: null vector");
+        outs.emplace_back((uintptr_t)p, (uintptr_t)p + n * 32);
+      }
+    }
+    with_field(field_id, [&](auto F) {
+      uint32_t w[8];
+      for (const void* s : {gamma, r}) {
+        memcpy(w, s, 32);
+        require(Fp<decltype(F)::value>::words_lt_p(w), NMX_E_SCALAR_RANGE, "nmx_ppsnark_mem_oracles: gamma or r >= field modulus");
+      }
+    });
+    // inputs may alias one another (they are only read); an output may touch neither an input nor another output
+    std::sort(outs.begin(), outs.end());
+    for (size_t i = 1; i < outs.size(); i++)
+      require(outs[i - 1].second <= outs[i].first, NMX_E_ARG, "nmx_ppsnark_mem_oracles: two outputs overlap");
+    for (const auto& o : outs)
+      for (const auto& in : ins)
+        require(!(o.first < in.second && in.first < o.second), NMX_E_ARG, "nmx_ppsnark_mem_oracles: an output overlaps an input");
+    CtxLease L;
+    if (!fv_ppsnark_mem_oracles(*L.c, field_id, k, n, mem, addr, L_, ts, gamma, r, flags, out_t_plus_r, out_w_plus_r, out_t_plus_r_inv,
+                                out_w_plus_r_inv))
+      throw Fail{NMX_E_ZERO, "nmx_ppsnark_mem_oracles: some T + r or W + r is zero (NovaError::InternalError, ppsnark.rs:430)"};
+  });
+}
+
 // Device state of one call that has to outlive the MSMs the call runs (they re-carve the context's arena): the context's aux buffer
 // up to kAuxMax bytes, an allocation of the call's own above that; carved front to back.  `ev`, if the call creates it, goes with it.
 struct CallScratch {

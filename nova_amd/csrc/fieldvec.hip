@@ -1336,10 +1336,53 @@ static void nifs_fold_t(Ctx& c, const void* w1, const void* w2, size_t n_w, cons
   timed_launch(c, f, n_w + n_e, &io);
 }
 
-// returns false when an element is zero (the reference: Err(NovaError::InternalError), spartan/mod.rs:103-105)
-template <int FID> static bool batch_invert_t(Ctx& c, const void* v, size_t n, uint32_t flags, void* out) {
+// Levels first .. L - 1 of Montgomery's trick forward, the top level on the host, and the same levels backward (sz[l]: the size of level l;
+// in[l]: its input, which is level l - 1's chunk products; res[l]: its prefix products, then its inverses).  batch_invert_t runs it from
+// level 0; a caller with a level 0 of its own (ppsnark_oracles.hpp) from level 1, between its forward and its backward pass.  false: an
+// element is zero -- nothing is in flight then (the stream was waited for before the top was read).
+template <int FID>
+static bool binv_levels(Ctx& c, DeviceBackend& be, const std::vector<size_t>& sz, const std::vector<const uint32_t*>& in,
+                        const std::vector<uint32_t*>& res, size_t first, bool mont) {
   using F = Fp<FID>;
   using H = HostFp4<FID>;
+  const size_t L = sz.size() - 1;
+  for (size_t l = first; l < L; l++) {
+    BatchInvFwdFn<FID> f{in[l], res[l], (uint32_t*)in[l + 1], (uint32_t)sz[l], (uint32_t)sz[l + 1], binv_chunk(sz[l])};
+    be.launch(f, (uint32_t)sz[l + 1]);
+  }
+  // top level on the host: out = Fm^2 / Y for every word Y (Fm = 1 or 2^256: the words' form; see the kernels' header)
+  const size_t nt = sz[L];
+  if (!c.pinned) HIPCHK(hipHostMalloc((void**)&c.pinned, DeviceBackend::kPinnedBytes, hipHostMallocDefault));
+  static_assert(2 * kBinvHostBelow * 32 <= DeviceBackend::kPinnedBytes, "the host level lives in the context's pinned buffer");
+  uint32_t *top = (uint32_t*)c.pinned, *topinv = top + 8 * kBinvHostBelow;
+  HIPCHK(hipMemcpyAsync(top, in[L], nt * 32, hipMemcpyDeviceToHost, c.stream));
+  stream_wait(c.stream);
+  {
+    std::vector<H> e(nt), pre(nt);
+    H acc = H::one();
+    for (size_t i = 0; i < nt; i++) {
+      if (!F::words_lt_p(top + 8 * i)) throw Fail{NMX_E_SCALAR_RANGE, "batch_invert: element >= field modulus"};
+      e[i] = H::from_canonical(top + 8 * i);  // the word as a plain value
+      pre[i] = acc;
+      acc = acc * e[i];
+    }
+    if (acc.is_zero()) return false;
+    H inv = acc.inv() * (mont ? H::pow2(512) : H::one());
+    for (size_t i = nt; i-- > 0;) {
+      (inv * pre[i]).to_canonical(topinv + 8 * i);
+      inv = inv * e[i];
+    }
+  }
+  HIPCHK(hipMemcpyAsync(res[L], topinv, nt * 32, hipMemcpyHostToDevice, c.stream));
+  for (size_t l = L; l-- > first;) {
+    BatchInvBwdFn<FID> f{in[l], res[l + 1], res[l], (uint32_t)sz[l], (uint32_t)sz[l + 1], binv_chunk(sz[l])};
+    be.launch(f, (uint32_t)sz[l + 1]);
+  }
+  return true;
+}
+
+// returns false when an element is zero (the reference: Err(NovaError::InternalError), spartan/mod.rs:103-105)
+template <int FID> static bool batch_invert_t(Ctx& c, const void* v, size_t n, uint32_t flags, void* out) {
   const bool mont = flags & NMX_SCALARS_MONT, dev = flags & NMX_SCALARS_DEVICE;
   // level sizes: n, ceil(n / K(n)), ... down to at most kBinvHostBelow
   std::vector<size_t> sz{n};
@@ -1371,38 +1414,7 @@ template <int FID> static bool batch_invert_t(Ctx& c, const void* v, size_t n, u
   const bool prof = G.profiling;
   DeviceBackend be(c, false, prof);
   be.mark("kernel");
-  for (size_t l = 0; l < L; l++) {
-    BatchInvFwdFn<FID> f{in[l], res[l], (uint32_t*)in[l + 1], (uint32_t)sz[l], (uint32_t)sz[l + 1], binv_chunk(sz[l])};
-    be.launch(f, (uint32_t)sz[l + 1]);
-  }
-  // top level on the host: out = Fm^2 / Y for every word Y (Fm = 1 or 2^256: the words' form; see the kernels' header)
-  const size_t nt = sz[L];
-  if (!c.pinned) HIPCHK(hipHostMalloc((void**)&c.pinned, DeviceBackend::kPinnedBytes, hipHostMallocDefault));
-  static_assert(2 * kBinvHostBelow * 32 <= DeviceBackend::kPinnedBytes, "the host level lives in the context's pinned buffer");
-  uint32_t *top = (uint32_t*)c.pinned, *topinv = top + 8 * kBinvHostBelow;
-  HIPCHK(hipMemcpyAsync(top, in[L], nt * 32, hipMemcpyDeviceToHost, c.stream));
-  stream_wait(c.stream);
-  {
-    std::vector<H> e(nt), pre(nt);
-    H acc = H::one();
-    for (size_t i = 0; i < nt; i++) {
-      if (!F::words_lt_p(top + 8 * i)) throw Fail{NMX_E_SCALAR_RANGE, "batch_invert: element >= field modulus"};
-      e[i] = H::from_canonical(top + 8 * i);  // the word as a plain value
-      pre[i] = acc;
-      acc = acc * e[i];
-    }
-    if (acc.is_zero()) return false;
-    H inv = acc.inv() * (mont ? H::pow2(512) : H::one());
-    for (size_t i = nt; i-- > 0;) {
-      (inv * pre[i]).to_canonical(topinv + 8 * i);
-      inv = inv * e[i];
-    }
-  }
-  HIPCHK(hipMemcpyAsync(res[L], topinv, nt * 32, hipMemcpyHostToDevice, c.stream));
-  for (size_t l = L; l-- > 0;) {
-    BatchInvBwdFn<FID> f{in[l], res[l + 1], res[l], (uint32_t)sz[l], (uint32_t)sz[l + 1], binv_chunk(sz[l])};
-    be.launch(f, (uint32_t)sz[l + 1]);
-  }
+  if (!binv_levels<FID>(c, be, sz, in, res, 0, mont)) return false;
   be.mark("end");
   if (!dev) HIPCHK(hipMemcpyAsync(out, res[0], n * 32, hipMemcpyDeviceToHost, c.stream));
   stream_wait(c.stream);
@@ -1910,3 +1922,4 @@ void fv_bind(Ctx& c, int field, const void* z, size_t z_len, size_t lo_off, size
 
 #include "r1cs_eval.hpp"
 #include "mercury.hpp"
+#include "ppsnark_oracles.hpp"

@@ -793,6 +793,13 @@ void fv_r1cs_evaluate(Ctx&, int field, const CsrView* mats, size_t k, const void
 void fv_mercury_h_poly(Ctx&, int field, const void* f, size_t n_rows, size_t n_cols, const void* eq_col, uint32_t flags, void* out_h);
 void fv_mercury_divide_by_binomial(Ctx&, int field, const void* f, size_t n_rows, size_t n_cols, const void* alpha, uint32_t flags,
                                    void* out_q, void* out_g);
+// ppsnark's lookup gather and fused logUp oracles (ppsnark_oracles.hpp).  Vectors follow NMX_SCALARS_DEVICE, gamma and r are host pointers;
+// synchronous.  fv_gather: false when an address is not below n_mem (or, Montgomery words, not below p); fv_ppsnark_mem_oracles: false when
+// some T + r or W + r is zero.  Shapes, NULLs, the scalars' range and overlaps are the caller's to check.
+bool fv_gather(Ctx&, int field, const void* mem, size_t n_mem, const void* addr, size_t n, uint32_t flags, void* out);
+bool fv_ppsnark_mem_oracles(Ctx&, int field, size_t k, size_t n, const void* const* mem, const void* const* addr, const void* const* L,
+                            const void* const* ts, const void* gamma, const void* r, uint32_t flags, void* const* out_t_plus_r,
+                            void* const* out_w_plus_r, void* const* out_t_plus_r_inv, void* const* out_w_plus_r_inv);
 void fv_nifs_fold(Ctx&, int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e, const void* r,
                   uint32_t flags, void* w, void* e);
 void fv_eq_evals(Ctx&, int field, const void* r_host, uint32_t ell, uint32_t flags, uint32_t* d_out);

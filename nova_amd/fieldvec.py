@@ -473,6 +473,36 @@ def mercury_quot_f(field, f, q, zeta_b_minus_alpha, zeta, mont=False):
     return out[1:], (out[0].cpu().numpy() if _is_device_tensor(out) else out[0]).tobytes()
 
 
+# ---- ppsnark's lookup gather and fused logUp oracles (src/spartan/ppsnark.rs:220-253, :371-489) ----------------------------------
+def gather(field, mem, addr, mont=False):
+    """evaluation_oracles' L_row = eq[row], L_col = z[col] (ppsnark.rs:220-253): out[i] = mem[addr[i]].  addr holds FIELD ELEMENTS whose
+    integer values are the addresses (the form row / col are committed in).  NmxError(E_ARG) when an address is not below len(mem)."""
+    pm, n_mem, dev, _km = _vec(mem)
+    pa, n, deva, _ka = _vec(addr)
+    assert dev == deva, "mem and addr both host or both HBM"
+    po, out = _out_like(dev, n, mem)
+    _check(L.lib().nmx_field_gather(field, pm, n_mem, pa, n, _flags(dev, mont), po))
+    return out
+
+
+def ppsnark_mem_oracles(field, mems, addrs, Ls, tss, gamma, r, mont=False):
+    """MemorySumcheckInstance::compute_oracles (ppsnark.rs:371-489) without its commitments, every memory in one call.  Returns per memory
+    (t_plus_r, w_plus_r, t_plus_r_inv, w_plus_r_inv): t_plus_r = mem gamma + i + r, w_plus_r = L gamma + addr + r, t_plus_r_inv =
+    ts / t_plus_r, w_plus_r_inv = 1 / w_plus_r.  NmxError(E_ZERO) when some t_plus_r or w_plus_r is zero."""
+    import ctypes
+    k = len(mems)
+    assert k == len(addrs) == len(Ls) == len(tss)
+    ins = [[_vec(x) for x in group] for group in (mems, addrs, Ls, tss)]
+    n, dev = (ins[0][0][1], ins[0][0][2]) if k else (0, False)
+    assert all(q[1] == n and q[2] == dev for group in ins for q in group), "every vector has n elements, all host or all HBM"
+    outs = [[_out_like(dev, n, mems[m]) for m in range(k)] for _ in range(4)]
+    arr = lambda ptrs: (ctypes.c_void_p * max(k, 1))(*ptrs)  # noqa: E731
+    g, rr = _chal(gamma), _chal(r)
+    _check(L.lib().nmx_ppsnark_mem_oracles(field, k, n, *[arr([q[0] for q in group]) for group in ins], g.ctypes.data, rr.ctypes.data,
+                                           _flags(dev, mont), *[arr([o[0] for o in group]) for group in outs]))
+    return [tuple(outs[j][m][1] for j in range(4)) for m in range(k)]
+
+
 # ---- Spartan's sum-check provers, one call each (nmx_sumcheck_prove_*; src/spartan/sumcheck.rs:199-507) ---------------------
 def as_transcript(fn):
     """fn(list of 32-byte coefficient strings) -> 32-byte challenge, wrapped as nmx_transcript_fn.  The transcript (Keccak on
