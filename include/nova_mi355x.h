@@ -313,7 +313,8 @@ int nmx_commit_finish(uint64_t ticket, uint8_t* out, uint8_t* out_is_inf);
  *     NMX_OP_CROSS_TERM  out = in0*in1 - u*in2 - in3       commit_T                   src/r1cs/mod.rs:614-620
  *     NMX_OP_CROSS_TERM2 out = in0*in1 - u*in2 - in3 - in4 commit_T_relaxed           src/r1cs/mod.rs:652-659
  *     NMX_OP_VEC_ADD out = in0 + in1                       Z = Z1 + Z2                src/r1cs/mod.rs:590-609
- *     (`challenge` = r or u, host pointer; operands and `out` must share one layout; out may be an operand)
+ *     (`challenge` = r or u, host pointer, < p; operands and `out` must share one layout; out may be an operand; operand words are
+ *     any 256-bit values read mod p and the output is canonical, as for the nmx_field_* calls below)
  *   nmx_msm_svec / nmx_commit_svec: nmx_msm_handle(key, 0, ..) / nmx_commit over the first n elements, the scalars taken
  *     shard by shard from the vector (it must have been allocated with n_key = the key's length). */
 enum { NMX_OP_AXPY = 0, NMX_OP_AXPY2 = 1, NMX_OP_CROSS_TERM = 2, NMX_OP_CROSS_TERM2 = 3, NMX_OP_VEC_ADD = 4 };
@@ -336,7 +337,13 @@ int nmx_point_sum(int curve, const uint8_t* partials128, size_t count, uint8_t* 
  * field ids: 0 = BN254 Fq (Grumpkin scalars), 1 = BN254 Fr (BN254 scalars), 2 = Pasta Fp (Vesta scalars),
  * 3 = Pasta Fq (Pallas scalars).  Vectors are n x 32 bytes; flags: NMX_SCALARS_MONT (vectors and the challenge
  * are raw Montgomery limbs), NMX_SCALARS_DEVICE (every vector pointer incl. `out` is an HBM pointer -- results
- * then stay resident for the next nmx_msm_handle(..., NMX_SCALARS_DEVICE)); the challenge is always a host pointer. */
+ * then stay resident for the next nmx_msm_handle(..., NMX_SCALARS_DEVICE)); the challenge is always a host pointer.
+ * OPERAND WORDS.  For nmx_field_axpy, nmx_field_axpy2, nmx_field_cross_term, nmx_field_cross_term2, nmx_field_vec_add,
+ * nmx_mle_bind_top, nmx_poly_fold_pairs, nmx_poly_fold_chain, nmx_field_lincomb_powers, nmx_nifs_fold, nmx_svec_map,
+ * nmx_sumcheck_eq_sums, nmx_sumcheck_bind_eq_sums and nmx_sumcheck_plain_sums every 32-byte word of an input VECTOR (eq tables
+ * included) may hold ANY 256-bit value w and is read as w mod p; every output word -- vector element, bound table entry or sum -- is
+ * canonical (< p).  (In the Montgomery layout w stands for w * 2^-256 mod p, whatever w is.)  A CHALLENGE (r, u, x, xs, s) must be
+ * < p: NMX_E_SCALAR_RANGE otherwise. */
 enum { NMX_F_BN254_FQ = 0, NMX_F_BN254_FR = 1, NMX_F_PASTA_FP = 2, NMX_F_PASTA_FQ = 3 };
 /* out = a + r*b : RelaxedR1CSWitness::fold, W = W1 + r*W2 and E = E1 + r*T (src/r1cs/mod.rs:1058-1067) */
 int nmx_field_axpy(int field, const void* a, const void* b, const void* r, size_t n, uint32_t flags, void* out);
@@ -383,14 +390,16 @@ int nmx_poly_fold_chain(int field, const void* p, size_t len, const void* xs, si
  *   mode 2 (A, B):    out = (sum (a0*b0 - 1)*factor,  sum (a1-a0)*(b1-b0)*factor)    cubic_with_two_inputs
  *   mode 1 (A):       out = (sum a0*factor, 0)                                        quadratic_with_one_input
  * out64 = two field elements in the vectors' own form (host pointer).  The O(1) derivation of the round polynomial
- * from these sums and the claim stays on the caller's side (sumcheck.rs:686-753). */
+ * from these sums and the claim stays on the caller's side (sumcheck.rs:686-753).  Words of A, B, C, eqL, eqR: any 256-bit values,
+ * read mod p; the sums are canonical. */
 int nmx_sumcheck_eq_sums(int field, int mode, const void* A, const void* B, const void* C, size_t len, const void* eqL,
                          size_t n_eqL, const void* eqR, size_t n_eqR, uint32_t shift, uint32_t flags, uint8_t* out64);
 /* One whole prover round in a single pass over HBM-resident tables (NMX_SCALARS_DEVICE required): bind A, B, C with
  * the round challenge r (bind_poly_var_top, src/spartan/polys/multilinear.rs:65-84, called at
  * src/spartan/sumcheck.rs:535-545) AND return the NEXT round's sums (t_0, t_inf) over the bound tables, exactly what
  * nmx_mle_bind_top x3 followed by nmx_sumcheck_eq_sums(mode, outA, outB, outC, len/2, ...) would give; the eq tables
- * are the next round's.  outX may equal X (in place, as the reference binds).  len % 4 == 0. */
+ * are the next round's.  outX may equal X (in place, as the reference binds).  len % 4 == 0.  Words of A, B, C, eqL, eqR: any 256-bit
+ * values, read mod p; the bound tables and the sums are canonical; r < p. */
 int nmx_sumcheck_bind_eq_sums(int field, int mode, const void* A, const void* B, const void* C, size_t len, const void* r,
                               const void* eqL, size_t n_eqL, const void* eqR, size_t n_eqR, uint32_t shift,
                               uint32_t flags, void* outA, void* outB, void* outC, uint8_t* out64);
@@ -399,7 +408,8 @@ int nmx_sumcheck_bind_eq_sums(int field, int mode, const void* A, const void* B,
  *   kind 2 (A, B)    linear     out = (sum a0 - b0,  sum A(-1) - B(-1))          src/spartan/sumcheck.rs:353-378
  *   kind 3 (A, B)    quadratic  out = (sum a0*b0,    sum A(-1)*B(-1))            src/spartan/sumcheck.rs:380-405
  *   kind 4 (A, B, C) cubic      out = (sum a0*b0*c0, sum dA*dB*dC, sum A(-1)*B(-1)*C(-1))   sumcheck.rs:407-443
- * out96 = three field elements (the third is zero for kinds 1-3), host pointer, in the vectors' own form. */
+ * out96 = three field elements (the third is zero for kinds 1-3), host pointer, in the vectors' own form.  Words of A, B, C: any
+ * 256-bit values, read mod p; the sums are canonical. */
 int nmx_sumcheck_plain_sums(int field, int kind, const void* A, const void* B, const void* C, size_t len, uint32_t flags,
                             uint8_t* out96);
 /* ---- Spartan's sum-check provers, ONE call each (BASELINE.json configs[4]; src/spartan/snark.rs:113-260) -------------------
@@ -443,7 +453,9 @@ int nmx_sumcheck_plain_sums(int field, int kind, const void* A, const void* B, c
  *  - nmx_sumcheck_prove_batch_eval == prove_batch_eval (sumcheck.rs:251-353; batch_eval_reduce, src/spartan/mod.rs:377-437):
  *    k <= 16 claims e_i = P_i(x_i), polys[i] of 2^num_rounds[i] elements (BOUND IN PLACE: the reference binds clones,
  *    spartan/mod.rs:407-410 -- pass copies to keep the originals), eq_points[i] = num_rounds[i] elements (host), claims and
- *    coeffs = k elements each (host), 3 coefficients per round over max(num_rounds) rounds, out_finals = [P_i(r_i)]. */
+ *    coeffs = k elements each (host), 3 coefficients per round over max(num_rounds) rounds, out_finals = [P_i(r_i)].
+ * OPERAND WORDS of the three provers: every word of a table, of taus, eq_points, claims and coeffs must be < p (the first round reads
+ * the tables as they are; unlike nmx_sumcheck_eq_sums / _bind_eq_sums / _plain_sums above, words >= p are NOT reduced here). */
 typedef int (*nmx_transcript_fn)(void* ctx, const uint8_t* coeffs32, size_t n_coeffs, uint8_t* challenge32_out);
 int nmx_sumcheck_prove_cubic_with_three_inputs(int field, const void* claim, const void* taus, size_t num_rounds, void* A, void* B,
                                                void* C, uint32_t flags, nmx_transcript_fn transcript, void* ctx, uint8_t* out_polys,

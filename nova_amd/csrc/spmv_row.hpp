@@ -3,12 +3,27 @@
 // (r1cs_eval.hpp) also compiles for the CPU under tests/host_emul; fieldvec.hip includes it first.
 #pragma once
 
+#include <cstddef>
+
 #include "fp.hpp"
 
 namespace nmx {
 
 template <int FID> NMX_HD Fp<FID> ld(const uint32_t* p, size_t i) { return Fp<FID>::from_words(p + 8 * i); }
 template <int FID> NMX_HD void st(uint32_t* p, size_t i, const Fp<FID>& v) { v.canon().to_words(p + 8 * i); }
+// Operands whose formula needs them below p (subtrahends of sub2, factors of two weakly reduced operands), loaded with ld from words
+// that may hold ANY 256-bit value (< 5.3 p): brought below p here.  A normalised v >= p has v.l[8] >= p's top limb, so ONE compare per
+// operand and one branch per group decide; behind it every operand of the group is canonicalised (the identity on those already
+// below p).  Canonical data -- the provers' -- almost never take the branch: its cost is N compares.
+template <int FID, int N> NMX_HD void below_p(Fp<FID> (&v)[N]) {
+  bool any = false;
+#pragma unroll
+  for (int j = 0; j < N; j++) any |= v[j].l[8] >= FpParams<FID>::P[8];
+  if (any) {
+#pragma unroll
+    for (int j = 0; j < N; j++) v[j] = v[j].canon();
+  }
+}
 
 // Coefficient classes, the GPU form of the reference's PrecomputedSparseMatrix (src/r1cs/sparse.rs:19-199: +-1 entries
 // are added / subtracted, |k| <= 7 by repeated doubling, the rest multiplied).  R1CS matrices are almost all +-1: here

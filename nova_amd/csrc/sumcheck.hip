@@ -15,12 +15,9 @@
 // every term carries the same power of the form factor, fixed by one constant multiplication on the host.
 #include "runtime.hpp"
 #include "host_fp4.hpp"
+#include "sumcheck_sums.hpp"  // ldw, eq_term and the lane bodies of the three sum passes
 
 namespace nmx {
-
-template <int FID> __device__ __forceinline__ Fp<FID> ldw(const uint32_t* p, size_t i) {
-  return Fp<FID>::from_words(p + 8 * i);
-}
 
 // tree-reduce `v` over the 256 lanes of a block; result valid in lane 0.  Values < 2p on entry.
 template <int FID> __device__ __forceinline__ Fp<FID> block_sum(Fp<FID> v, uint32_t* lds /* 256 x 9 */) {
@@ -129,62 +126,14 @@ template <int FID, int J, int STRIDE> __global__ __launch_bounds__(256) void k_s
   }
 }
 
-// The terms of one index: e0 = a0*b0 - c0 (at product scale) and q = (a1-a0)*(b1-b0), with the eq factor.
-template <int FID, int MODE> struct EqTerm {
-  Fp<FID> e0, q, fac;
-};
-template <int FID, int MODE>
-__device__ __forceinline__ EqTerm<FID, MODE> eq_term(const uint32_t* A, const uint32_t* B, const uint32_t* C,
-                                                     const uint32_t* eqL, const uint32_t* eqR, uint32_t shift,
-                                                     uint32_t mask, uint32_t h, const Fp<FID>& nk, uint32_t id,
-                                                     uint32_t eq_index = 0xffffffffu) {
-  using F = Fp<FID>;
-  EqTerm<FID, MODE> t;
-  // eq_index given (k_eq_rows): the factor is eqR[eq_index] alone, eqL is applied once per row by the caller
-  t.fac = ldw<FID>(eqR, eq_index != 0xffffffffu ? eq_index : (eqL ? (id & mask) : id));
-  if (eqL) t.fac = ldw<FID>(eqL, id >> shift) * t.fac;
-  const F a0 = ldw<FID>(A, id);
-  if (MODE == 1) {
-    t.e0 = a0;
-    t.q = F::zero();
-  } else {
-    const F a1 = ldw<FID>(A, (size_t)id + h), b0 = ldw<FID>(B, id), b1 = ldw<FID>(B, (size_t)id + h);
-    // a0*b0 - c0*k in ONE reduction: nk = p - k (k brings c0 to the scale of a product; MODE 2: c0 = 1 folded into nk)
-    t.e0 = MODE == 3 ? F::mul_add(a0, b0, ldw<FID>(C, id), nk) : (a0 * b0 + nk).norm();   // < 1.02 p / < 2.01 p
-    t.q = F::sub2(a1, a0).norm() * F::sub2(b1, b0).norm();                                 // operands < 3 p
-  }
-  return t;
-}
-
 template <int FID, int MODE>
 __global__ __launch_bounds__(256) void k_eq_sums(const uint32_t* A, const uint32_t* B, const uint32_t* C,
                                                  const uint32_t* eqL, const uint32_t* eqR, uint32_t shift, uint32_t mask,
                                                  uint32_t h, Fp<FID> nk, uint32_t* partial) {
   using F = Fp<FID>;
   __shared__ uint32_t lds[9 * 256];
-  F s0 = F::zero(), s1 = F::zero();
-  uint32_t pending = 0;  // lazily added terms since the last canonicalisation (each < 1.1 p, limbs < 2^29)
-  const uint32_t stride = gridDim.x * 256u;
-  uint32_t id = blockIdx.x * 256u + threadIdx.x;
-  // two indices per iteration: s += e_i * f_i + e_j * f_j is one reduction for two products
-  for (; id + stride < h; id += 2 * stride) {
-    const EqTerm<FID, MODE> x = eq_term<FID, MODE>(A, B, C, eqL, eqR, shift, mask, h, nk, id);
-    const EqTerm<FID, MODE> y = eq_term<FID, MODE>(A, B, C, eqL, eqR, shift, mask, h, nk, id + stride);
-    s0 = s0 + F::mul_add(x.e0, x.fac, y.e0, y.fac);            // < p (1 + 2 * 2.1 * 1.1 / 127)
-    if (MODE != 1) s1 = s1 + F::mul_add(x.q, x.fac, y.q, y.fac);
-    if (++pending == 6) {  // 1 canonical + 6 fresh terms: value < 8 p, limbs < 7 * 2^29 -- then back to < p
-      s0 = s0.norm().canon();
-      s1 = s1.norm().canon();
-      pending = 0;
-    }
-  }
-  if (id < h) {
-    const EqTerm<FID, MODE> x = eq_term<FID, MODE>(A, B, C, eqL, eqR, shift, mask, h, nk, id);
-    s0 = s0 + x.e0 * x.fac;
-    if (MODE != 1) s1 = s1 + x.q * x.fac;
-  }
-  s0 = s0.norm().canon();
-  s1 = s1.norm().canon();
+  F s0, s1;
+  eq_sums_lane<FID, MODE>(A, B, C, eqL, eqR, shift, mask, h, nk, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, s0, s1);
   s0 = block_sum<FID>(s0, lds);
   if (MODE != 1) {
     __syncthreads();
@@ -211,71 +160,8 @@ __global__ __launch_bounds__(256, NMX_EQROWS_MINWAVES) void k_eq_rows(const uint
                                                  uint32_t* partial) {
   using F = Fp<FID>;
   __shared__ uint32_t lds[9 * 256];
-  const uint32_t row = 1u << shift, P = row < 256u ? row : 256u, rows_per_block = 256u / P, K = row / P;
-  const uint32_t t = threadIdx.x, lo0 = t % P, sub = t / P;
-  const uint32_t nrows = (uint32_t)(((uint64_t)h + row - 1) >> shift);
-  F g0 = F::zero(), g1 = F::zero();
-  uint32_t pend_g = 0;
-  for (uint32_t hi = blockIdx.x * rows_per_block + sub; hi < nrows; hi += gridDim.x * rows_per_block) {
-    const uint32_t base = hi << shift;
-    F r0 = F::zero(), r1 = F::zero();
-    uint32_t pend = 0, k = 0;
-    // mode 1 (evaluate_with): four indices per reduction (Fp::dot), whole groups inside the vector.  (Modes 2 / 3 would hold
-    // twelve operands -- 221 registers, two waves per SIMD -- for 6 % fewer multiply-adds: they keep the pairs below.)
-    if constexpr (MODE == 1) {
-      for (; k + 3 < K; k += 4) {
-        const uint32_t l0 = lo0 + k * P;
-        if (base + l0 + 3 * P >= h) break;
-        F e[4], fc[4];
-#pragma unroll
-        for (uint32_t j = 0; j < 4; j++) {
-          e[j] = ldw<FID>(A, base + l0 + j * P);
-          fc[j] = ldw<FID>(eqR, l0 + j * P);
-        }
-        r0 = r0 + F::template dot<4>(e, fc);  // < 1.04 p
-        if (++pend == 6) {
-          r0 = r0.norm().canon();
-          pend = 0;
-        }
-      }
-    }
-    for (; k + 1 < K; k += 2) {  // two indices per reduction
-      const uint32_t l0 = lo0 + k * P, l1 = l0 + P;
-      if (base + l1 < h) {
-        const EqTerm<FID, MODE> x = eq_term<FID, MODE>(A, B, C, nullptr, eqR, 0, 0, h, nk, base + l0, l0);
-        const EqTerm<FID, MODE> y = eq_term<FID, MODE>(A, B, C, nullptr, eqR, 0, 0, h, nk, base + l1, l1);
-        r0 = r0 + F::mul_add(x.e0, x.fac, y.e0, y.fac);
-        if (MODE != 1) r1 = r1 + F::mul_add(x.q, x.fac, y.q, y.fac);
-      } else if (base + l0 < h) {
-        const EqTerm<FID, MODE> x = eq_term<FID, MODE>(A, B, C, nullptr, eqR, 0, 0, h, nk, base + l0, l0);
-        r0 = r0 + x.e0 * x.fac;
-        if (MODE != 1) r1 = r1 + x.q * x.fac;
-      }
-      if (++pend == 6) {
-        r0 = r0.norm().canon();
-        r1 = r1.norm().canon();
-        pend = 0;
-      }
-    }
-    if (k < K) {
-      const uint32_t l0 = lo0 + k * P;
-      if (base + l0 < h) {
-        const EqTerm<FID, MODE> x = eq_term<FID, MODE>(A, B, C, nullptr, eqR, 0, 0, h, nk, base + l0, l0);
-        r0 = r0 + x.e0 * x.fac;
-        if (MODE != 1) r1 = r1 + x.q * x.fac;
-      }
-    }
-    const F el = ldw<FID>(eqL, hi);
-    g0 = g0 + r0.norm().canon() * el;
-    if (MODE != 1) g1 = g1 + r1.norm().canon() * el;
-    if (++pend_g == 6) {
-      g0 = g0.norm().canon();
-      g1 = g1.norm().canon();
-      pend_g = 0;
-    }
-  }
-  g0 = g0.norm().canon();
-  g1 = g1.norm().canon();
+  F g0, g1;
+  eq_rows_lane<FID, MODE>(A, B, C, eqL, eqR, shift, h, nk, threadIdx.x, blockIdx.x, gridDim.x, g0, g1);
   if constexpr (MODE == 1) {  // one sum only (g1 stays zero): at 2^20 the block sum is 40 % of this kernel's instructions
     F x[1] = {g0};
     block_sum_waves<FID, 1>(x, lds);
@@ -410,41 +296,12 @@ __global__ __launch_bounds__(256) void k_bind_eq_sums(const uint32_t* A, const u
                                                       uint32_t mask, uint32_t hq, Fp<FID> nk, uint32_t* partial) {
   using F = Fp<FID>;
   __shared__ uint32_t lds[9 * 256];
-  F s0 = F::zero(), s1 = F::zero();
-  uint32_t pending = 0;
-  auto bind2 = [&](const uint32_t* X, uint32_t* oX, uint32_t id, F& y0, F& y1) {
-    const F x00 = ldw<FID>(X, id), x01 = ldw<FID>(X, (size_t)id + hq);
-    const F x10 = ldw<FID>(X, (size_t)id + 2 * (size_t)hq), x11 = ldw<FID>(X, (size_t)id + 3 * (size_t)hq);
-    y0 = (x00 + r * F::sub2(x10, x00).norm()).norm().canon();   // lo + r * (hi - lo), as BindTopFn
-    y1 = (x01 + r * F::sub2(x11, x01).norm()).norm().canon();
-    y0.to_words(oX + 8 * (size_t)id);
-    y1.to_words(oX + 8 * ((size_t)id + hq));
-  };
-  for (uint32_t id = blockIdx.x * 256u + threadIdx.x; id < hq; id += gridDim.x * 256u) {
-    F a0, a1, b0, b1, c0, c1;
-    bind2(A, oA, id, a0, a1);
-    if (MODE >= 2) bind2(B, oB, id, b0, b1);
-    if (MODE == 3) bind2(C, oC, id, c0, c1);
-    F fac = ldw<FID>(eqR, eqL ? (id & mask) : id);
-    if (eqL) fac = ldw<FID>(eqL, id >> shift) * fac;
-    if (MODE == 1) {
-      s0 = s0 + a0 * fac;
-    } else {
-      const F e0 = MODE == 3 ? F::mul_add(a0, b0, c0, nk) : (a0 * b0 + nk).norm();  // a0*b0 - c0*k, one reduction
-      const F q = F::sub2(a1, a0).norm() * F::sub2(b1, b0).norm();
-      s0 = s0 + e0 * fac;
-      s1 = s1 + q * fac;
-    }
-    if (++pending == 6) {
-      s0 = s0.norm().canon();
-      s1 = s1.norm().canon();
-      pending = 0;
-    }
-  }
-  s0 = block_sum<FID>(s0.norm().canon(), lds);
+  F s0, s1;
+  bind_eq_sums_lane<FID, MODE>(A, B, C, oA, oB, oC, r, eqL, eqR, shift, mask, hq, nk, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, s0, s1);
+  s0 = block_sum<FID>(s0, lds);
   if (MODE != 1) {
     __syncthreads();
-    s1 = block_sum<FID>(s1.norm().canon(), lds);
+    s1 = block_sum<FID>(s1, lds);
   }
   if (threadIdx.x == 0) {
     s0.to_words(partial + 16 * blockIdx.x);
@@ -705,61 +562,14 @@ __global__ __launch_bounds__(256) void k_plain_sums(const uint32_t* A, const uin
                                                     uint32_t* partial /* 32 words per block */) {
   using F = Fp<FID>;
   __shared__ uint32_t lds[9 * 256];
-  F s0 = F::zero(), s1 = F::zero(), s2 = F::zero();
-  uint32_t pending = 0;
-  const uint32_t stride = gridDim.x * 256u;
-  uint32_t id = blockIdx.x * 256u + threadIdx.x;
-  if constexpr (KIND == 1 || KIND == 3) {
-    // two indices per reduction (mul_add: 2 x 81 + 81 multiply-adds instead of 2 x 162)
-    for (; (uint64_t)id + stride < h; id += 2 * stride) {
-      const uint32_t jd = id + stride;
-      const F a0 = ldw<FID>(A, id), a1 = ldw<FID>(A, (size_t)id + h), b0 = ldw<FID>(B, id), b1 = ldw<FID>(B, (size_t)id + h);
-      const F c0 = ldw<FID>(A, jd), c1 = ldw<FID>(A, (size_t)jd + h), d0 = ldw<FID>(B, jd), d1 = ldw<FID>(B, (size_t)jd + h);
-      s0 = s0 + F::mul_add(a0, b0, c0, d0);
-      if (KIND == 1)
-        s1 = s1 + F::mul_add(F::sub2(a1, a0).norm(), F::sub2(b1, b0).norm(), F::sub2(c1, c0).norm(), F::sub2(d1, d0).norm());  // operands < 3 p -> < 1.15 p
-      else
-        s1 = s1 + F::mul_add(F::sub2(a0.dbl(), a1).norm(), F::sub2(b0.dbl(), b1).norm(), F::sub2(c0.dbl(), c1).norm(),
-                             F::sub2(d0.dbl(), d1).norm());  // operands < 4 p -> < 1.26 p
-      if (++pending == 6) {
-        s0 = s0.norm().canon();
-        s1 = s1.norm().canon();
-        pending = 0;
-      }
-    }
-  }
-  for (; id < h; id += stride) {
-    const F a0 = ldw<FID>(A, id), a1 = ldw<FID>(A, (size_t)id + h);
-    const F b0 = ldw<FID>(B, id), b1 = ldw<FID>(B, (size_t)id + h);
-    if (KIND == 1) {
-      s0 = s0 + a0 * b0;
-      s1 = s1 + F::sub2(a1, a0).norm() * F::sub2(b1, b0).norm();          // operands < 3 p -> < 1.08 p
-    } else if (KIND == 2) {
-      s0 = s0 + F::sub2(a0, b0);                                          // < 3 p
-      s1 = s1 + F::sub4(F::sub2(a0.dbl(), a1).norm(), F::sub2(b0.dbl(), b1).norm());  // < 4p + 4p
-    } else if (KIND == 3) {
-      s0 = s0 + a0 * b0;
-      s1 = s1 + F::sub2(a0.dbl(), a1).norm() * F::sub2(b0.dbl(), b1).norm();  // operands < 4 p -> < 1.13 p
-    } else {
-      const F c0 = ldw<FID>(C, id), c1 = ldw<FID>(C, (size_t)id + h);
-      s0 = s0 + (a0 * b0) * c0;
-      s1 = s1 + (F::sub2(a1, a0).norm() * F::sub2(b1, b0).norm()) * F::sub2(c1, c0).norm();
-      s2 = s2 + (F::sub2(a0.dbl(), a1).norm() * F::sub2(b0.dbl(), b1).norm()) * F::sub2(c0.dbl(), c1).norm();
-    }
-    // kind 2 adds up to 8 p per term (limbs < 2^31): canonicalise every term; products add < 1.2 p (limbs < 2^29)
-    if (KIND == 2 || ++pending == 6) {
-      s0 = s0.norm().canon();
-      s1 = s1.norm().canon();
-      if (KIND == 4) s2 = s2.norm().canon();
-      pending = 0;
-    }
-  }
-  s0 = block_sum<FID>(s0.norm().canon(), lds);
+  F s0, s1, s2;
+  plain_sums_lane<FID, KIND>(A, B, C, h, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, s0, s1, s2);
+  s0 = block_sum<FID>(s0, lds);
   __syncthreads();
-  s1 = block_sum<FID>(s1.norm().canon(), lds);
+  s1 = block_sum<FID>(s1, lds);
   if (KIND == 4) {
     __syncthreads();
-    s2 = block_sum<FID>(s2.norm().canon(), lds);
+    s2 = block_sum<FID>(s2, lds);
   }
   if (threadIdx.x == 0) {
     s0.to_words(partial + 32 * blockIdx.x);
