@@ -340,10 +340,12 @@ int nmx_point_sum(int curve, const uint8_t* partials128, size_t count, uint8_t* 
  * then stay resident for the next nmx_msm_handle(..., NMX_SCALARS_DEVICE)); the challenge is always a host pointer.
  * OPERAND WORDS.  For nmx_field_axpy, nmx_field_axpy2, nmx_field_cross_term, nmx_field_cross_term2, nmx_field_vec_add,
  * nmx_mle_bind_top, nmx_poly_fold_pairs, nmx_poly_fold_chain, nmx_field_lincomb_powers, nmx_nifs_fold, nmx_svec_map,
- * nmx_sumcheck_eq_sums, nmx_sumcheck_bind_eq_sums and nmx_sumcheck_plain_sums every 32-byte word of an input VECTOR (eq tables
- * included) may hold ANY 256-bit value w and is read as w mod p; every output word -- vector element, bound table entry or sum -- is
- * canonical (< p).  (In the Montgomery layout w stands for w * 2^-256 mod p, whatever w is.)  A CHALLENGE (r, u, x, xs, s) must be
- * < p: NMX_E_SCALAR_RANGE otherwise. */
+ * nmx_sumcheck_eq_sums, nmx_sumcheck_bind_eq_sums, nmx_sumcheck_plain_sums, nmx_field_batch_invert (v), nmx_mle_evaluate (z),
+ * nmx_mle_multi_evaluate (zs) and nmx_poly_eval_multi (polys) every 32-byte word of an input VECTOR (eq tables
+ * included) may hold ANY 256-bit value w and is read as w mod p; every output word -- vector element, bound table entry, sum or
+ * evaluation -- is canonical (< p).  (In the Montgomery layout w stands for w * 2^-256 mod p, whatever w is.)  A CHALLENGE or POINT
+ * (r, u, x, xs, s, points; every coordinate of r for nmx_eq_evals_from_points, nmx_mle_evaluate and nmx_mle_multi_evaluate) must be
+ * < p: NMX_E_SCALAR_RANGE otherwise, found before anything is launched, and nothing is written. */
 enum { NMX_F_BN254_FQ = 0, NMX_F_BN254_FR = 1, NMX_F_PASTA_FP = 2, NMX_F_PASTA_FQ = 3 };
 /* out = a + r*b : RelaxedR1CSWitness::fold, W = W1 + r*W2 and E = E1 + r*T (src/r1cs/mod.rs:1058-1067) */
 int nmx_field_axpy(int field, const void* a, const void* b, const void* r, size_t n, uint32_t flags, void* out);
@@ -360,9 +362,11 @@ int nmx_field_cross_term2(int field, const void* az, const void* bz, const void*
 /* out = a + b : Z = Z1 + Z2 (src/r1cs/mod.rs:590-609) */
 int nmx_field_vec_add(int field, const void* a, const void* b, size_t n, uint32_t flags, void* out);
 /* batch_invert (src/spartan/mod.rs:54-118; callers: ppsnark's lookup argument src/spartan/ppsnark.rs:430, IPA src/provider/
- * ipa_pc.rs:328): out[i] = 1 / v[i].  NMX_E_ZERO when an element is zero (the reference returns Err(NovaError::InternalError)) --
- * nothing meaningful is written then.  Montgomery's trick level by level on the device (strided 8..32-element chunks per lane), the
- * top <= 128 products inverted on the host.  `out` must not overlap `v`. */
+ * ipa_pc.rs:328): out[i] = 1 / v[i].  A word of v is ANY 256-bit value w, read as w mod p at every n (OPERAND WORDS above); the
+ * outputs are canonical.  NMX_E_ZERO when an element is zero mod p -- the words 0, p, 2p, ... below 2^256 -- at every n (the reference
+ * returns Err(NovaError::InternalError)); nothing meaningful is written then.  Montgomery's trick level by level on the device
+ * (strided 8..32-element chunks per lane), the top <= 128 products (for n <= 128: the elements themselves, reduced mod p first)
+ * inverted on the host.  `out` must not overlap `v`. */
 int nmx_field_batch_invert(int field, const void* v, size_t n, uint32_t flags, void* out);
 /* out[n_out] = parts[0] || parts[1] || ... || 0 ... 0 for vectors that live in HBM: Spartan's `z = [W.W, vec![U.u], U.X].concat()`
  * then `z.resize(2 * num_vars, 0)` (src/spartan/snark.rs:133, 193-196), and -- with one part -- the clones batch_eval_reduce
@@ -661,7 +665,9 @@ int nmx_poly_suffix_horner(int field, const void* f, size_t n, const void* u, ui
 /* HyperKZG's evaluation matrix (src/provider/hyperkzg.rs:1011-1020 `poly_eval`, called for every folded polynomial at
  * the three points r, -r, r^2, :1049-1056): out[i * m + j] = polys[i](points[j]) for k polynomials of any lengths
  * (coefficients low to high; an empty polynomial evaluates to 0) at m <= 4 points, all in one launch.  `polys`, `lens`,
- * `points` and `out` are host arrays; the coefficient vectors follow NMX_SCALARS_DEVICE. */
+ * `points` and `out` are host arrays; the coefficient vectors follow NMX_SCALARS_DEVICE.  A coefficient word is ANY 256-bit value
+ * w, read as w mod p; the outputs are canonical (OPERAND WORDS above).  A point >= p: NMX_E_SCALAR_RANGE, before anything is staged or
+ * launched, `out` untouched.  m > 4 or k > 4096: NMX_E_TOO_LARGE. */
 int nmx_poly_eval_multi(int field, const void* const* polys, const size_t* lens, size_t k, const void* points, size_t m,
                         uint32_t flags, uint8_t* out);
 /* ---- Mercury's prover passes (the second evaluation engine on BN254, src/provider/mercury.rs) -----------------------------------
@@ -693,12 +699,17 @@ int nmx_mercury_h_poly(int field_id, const void* f, size_t n_rows, size_t n_cols
 int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, size_t n_cols, const void* alpha,
                                    uint32_t flags, void* out_q /* (n_rows - 1) * n_cols */, void* out_g /* n_cols */);
 /* EqPolynomial::evals_from_points (src/spartan/polys/eq.rs:54-73): out[2^ell] = eq(r, x) for x in {0,1}^ell, r[0] the
- * most significant variable.  r: ell x 32 bytes, host.  out: host, or HBM with NMX_SCALARS_DEVICE. */
+ * most significant variable.  r: ell x 32 bytes, host.  out: host, or HBM with NMX_SCALARS_DEVICE; every entry canonical, in the
+ * layout `flags` names (Montgomery: eq * 2^256 mod p).  ell >= 31: NMX_E_ARG.  A coordinate r[i] >= p: NMX_E_SCALAR_RANGE, found
+ * before anything is launched; `out` is not written. */
 int nmx_eq_evals_from_points(int field, const void* r, size_t ell, uint32_t flags, void* out);
-/* MultilinearPolynomial::evaluate / evaluate_with (src/spartan/polys/multilinear.rs:88-129): Z(r), len == 2^ell. */
+/* MultilinearPolynomial::evaluate / evaluate_with (src/spartan/polys/multilinear.rs:88-129): Z(r), len == 2^ell (NMX_E_ARG otherwise).
+ * A word of z is ANY 256-bit value w, read as w mod p, for host and HBM operands alike and at every ell; the result is canonical
+ * (OPERAND WORDS above).  z is only read, and never past z[len).  A coordinate r[i] >= p: NMX_E_SCALAR_RANGE, nothing is written. */
 int nmx_mle_evaluate(int field, const void* z, size_t len, const void* r, size_t ell, uint32_t flags, uint8_t* out32);
 /* MultilinearPolynomial::multi_evaluate_with (src/spartan/polys/multilinear.rs:131-180): k polynomials of the same
- * length 2^ell at one point; the eq tables are built once.  out = k x 32 bytes (host). */
+ * length 2^ell at one point; the eq tables are built once.  out = k x 32 bytes (host).  Words of the zs, results and errors as
+ * for nmx_mle_evaluate: out[j] equals what nmx_mle_evaluate gives for zs[j]. */
 int nmx_mle_multi_evaluate(int field, const void* const* zs, size_t k, size_t len, const void* r, size_t ell,
                            uint32_t flags, uint8_t* out);
 /* SparseMatrix (CSR, scipy naming: data / indices / indptr, src/r1cs/sparse.rs:232-260) resident in HBM, and

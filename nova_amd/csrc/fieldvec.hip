@@ -18,122 +18,9 @@
 #include "host_fp4.hpp"
 #include "spmv_row.hpp"  // ld / st, the coefficient classes, spmv_row
 #include "fieldvec_maps.hpp"  // AxpyFn, Axpy2Fn, CrossTermFn, CrossTerm2Fn, VecAddFn, BindTopFn, FoldPairFn, LinCombFn
+#include "fieldvec_eval.hpp"  // the eq-table functors, BatchInvFwdFn / BatchInvBwdFn, binv_chunk, kBinvHostBelow
 
 namespace nmx {
-
-// EqPolynomial::evals_from_points, one doubling step (/root/reference/src/spartan/polys/eq.rs:54-73):
-//   y = x[i] * r;  x[i + size] = y;  x[i] -= y        for i < size
-template <int FID> struct EqStepFn {
-  uint32_t* buf;
-  Fp<FID> r;  // r * 2^261
-  uint32_t size;
-  NMX_HD void operator()(uint32_t i) const {
-    using F = Fp<FID>;
-    F x = ld<FID>(buf, i);
-    F y = r * x;                                   // < 1.01 p
-    st<FID>(buf, (size_t)i + size, y);
-    st<FID>(buf, i, F::sub2(x, y).norm());         // x - y + 2p
-  }
-};
-
-// Small eq tables in ONE launch: out[x] = prod_i (x_i ? r_i : 1 - r_i), x_0 the most significant bit, ell <= 12
-// (the sqrt-size tables of evaluate_with: ell doubling launches are ~10 us each, this is one).  ell modmuls per entry
-// instead of one -- irrelevant at <= 4096 entries.
-template <int FID> struct EqDirectFn {
-  static constexpr uint32_t kMaxEll = 12;
-  uint32_t* out;
-  Fp<FID> r[kMaxEll], nr[kMaxEll];  // r_i * 2^261 and (1 - r_i) * 2^261, canonical
-  Fp<FID> one;                      // ONE in the vectors' form (1 or 2^256 mod p), as a plain residue
-  uint32_t ell;
-  NMX_HD void operator()(uint32_t x) const {
-    Fp<FID> acc = one;
-    for (uint32_t i = 0; i < ell; i++) acc = acc * (((x >> (ell - 1 - i)) & 1u) ? r[i] : nr[i]);
-    st<FID>(out, x, acc);
-  }
-};
-
-// Both sqrt-size tables of an evaluation (multilinear.rs:141-147) in ONE launch: lanes [0, 2^ellL) build the left table, the rest
-// the right one (a 2^20 evaluation was four launches -- two tables, the pass, the final sum -- for 28 us; now two).
-template <int FID> struct EqDirect2Fn {
-  uint32_t *outL, *outR;
-  Fp<FID> r[2 * EqDirectFn<FID>::kMaxEll], nr[2 * EqDirectFn<FID>::kMaxEll];  // left challenges, then the right ones
-  Fp<FID> one;
-  uint32_t ellL, ellR;
-  NMX_HD void operator()(uint32_t g) const {
-    const bool right = g >= (1u << ellL);
-    const uint32_t x = right ? g - (1u << ellL) : g, ell = right ? ellR : ellL, o = right ? ellL : 0u;
-    Fp<FID> acc = one;
-    for (uint32_t i = 0; i < ell; i++) acc = acc * (((x >> (ell - 1 - i)) & 1u) ? r[o + i] : nr[o + i]);
-    st<FID>(right ? outR : outL, x, acc);
-  }
-};
-
-// batch_invert (src/spartan/mod.rs:54-118: Montgomery's trick, chunked over threads there).  Here a lane owns the STRIDED chunk
-// {c, c + T, c + 2T, ...} of K elements (T = number of chunks: consecutive lanes touch consecutive elements), a forward pass
-// leaves every element's prefix product in `out` and the chunk products in a vector that is inverted the same way one level up
-// (the last level, <= 128 products, on the host: one extended-Euclid inversion), and a backward pass per level turns prefix
-// products into inverses.  All products are taken on the stored words as they are (canonical or Montgomery): the form factor is
-// a scale the top level applies once, and every lower level inherits it through the chunk inverses.
-// Cost: 3 products per element at level 0 (the trick's minimum) + 3/K of that above it -- VALU-bound for long vectors (2^24:
-// 52 ps per element = 3.1 products at the multiplier's ~58 G/s; the 160 B per element of traffic would take 20 ps), and a chain
-// of 3K DEPENDENT products per level for short ones, which is why K shrinks with the level's size (binv_chunk).
-static constexpr uint32_t kBinvHostBelow = 128;
-static inline uint32_t binv_chunk(size_t n) { return n >= (1u << 23) ? 32 : n >= (1u << 21) ? 16 : 8; }
-template <int FID> struct BatchInvFwdFn {
-  const uint32_t* v;
-  uint32_t *prefix, *chunk_prod;
-  uint32_t n, T, K;
-  NMX_HD void operator()(uint32_t c) const {
-    Fp<FID> acc = Fp<FID>::one();
-    for (uint32_t j = 0; j < K; j++) {
-      const uint64_t i = (uint64_t)c + (uint64_t)j * T;
-      if (i >= n) break;
-      st<FID>(prefix, i, acc);
-      acc = acc * ld<FID>(v, i);
-    }
-    st<FID>(chunk_prod, c, acc);
-  }
-};
-template <int FID> struct BatchInvBwdFn {
-  const uint32_t *v, *chunk_inv;
-  uint32_t* prefix;  // in: prefix products; out: the inverses
-  uint32_t n, T, K;
-  NMX_HD void operator()(uint32_t c) const {
-    Fp<FID> acc = ld<FID>(chunk_inv, c);
-    uint32_t cnt = 0;
-    while (cnt < K && (uint64_t)c + (uint64_t)cnt * T < n) cnt++;
-    for (uint32_t j = cnt; j-- > 0;) {
-      const uint64_t i = (uint64_t)c + (uint64_t)j * T;
-      const Fp<FID> p = ld<FID>(prefix, i), w = ld<FID>(v, i);
-      st<FID>(prefix, i, acc * p);
-      acc = (acc * w).canon();
-    }
-  }
-};
-
-// Large eq tables (13 <= ell <= 24) in TWO launches instead of ell doubling steps (a 2^20 table was 20 dependent launches,
-// ~130 us, for 32 MB of output: profiles/r05_spartan): the sqrt-size tables of the two halves of the point -- the left one in the
-// INTERNAL form, so that one product per entry gives out[x] = L[x >> ellR] * R[x & mask] in the vectors' own form -- and the
-// product pass.  compute_eval_table_sparse's operand (src/spartan/snark.rs:182) is such a table.
-template <int FID> struct EqSplit2Fn {
-  uint32_t *outL, *outR;
-  Fp<FID> r[2 * EqDirectFn<FID>::kMaxEll], nr[2 * EqDirectFn<FID>::kMaxEll];
-  Fp<FID> oneL, oneR;
-  uint32_t ellL, ellR;
-  NMX_HD void operator()(uint32_t g) const {
-    const bool right = g >= (1u << ellL);
-    const uint32_t x = right ? g - (1u << ellL) : g, ell = right ? ellR : ellL, o = right ? ellL : 0u;
-    Fp<FID> acc = right ? oneR : oneL;
-    for (uint32_t i = 0; i < ell; i++) acc = acc * (((x >> (ell - 1 - i)) & 1u) ? r[o + i] : nr[o + i]);
-    st<FID>(right ? outR : outL, x, acc);
-  }
-};
-template <int FID> struct EqProductFn {
-  const uint32_t *L, *R;
-  uint32_t* out;
-  uint32_t shift, mask;
-  NMX_HD void operator()(uint32_t x) const { st<FID>(out, x, ld<FID>(L, x >> shift) * ld<FID>(R, x & mask)); }
-};
 
 // (the coefficient classes and kSpmvColBits: spmv_row.hpp)
 template <int FID> struct SpmvClassifyFn {  // after the coefficients are in internal form; writes the class into indices
@@ -861,6 +748,15 @@ template <int FID> static Fp<FID> challenge(const void* r, bool mont) {
   return (mont ? f.mont256_to_internal() : f.to_internal()).canon();
 }
 
+// every coordinate of a point below p, or NMX_E_SCALAR_RANGE -- before a call enqueues or writes anything
+template <int FID> static void challenges_in_range(const void* r, size_t count) {
+  for (size_t i = 0; i < count; i++) {
+    uint32_t w[8];
+    memcpy(w, (const uint8_t*)r + 32 * i, 32);
+    require(Fp<FID>::words_lt_p(w), NMX_E_SCALAR_RANGE, "challenge >= field modulus");
+  }
+}
+
 struct VecIO {  // stages host vectors through the context arena; device vectors are used in place
   Ctx& c;
   bool dev;
@@ -970,6 +866,7 @@ template <int FID> struct FieldImpl {
 template <int FID> static void eq_evals_t(Ctx& c, const void* r_host, uint32_t ell, uint32_t flags, uint32_t* d_out) {
   using F = Fp<FID>;
   const bool mont = flags & NMX_SCALARS_MONT;
+  challenges_in_range<FID>(r_host, ell);
   // evals[0] = ONE in the vectors' form: 1, or 2^256 mod p
   F one = F::zero();
   one.l[0] = 1;
@@ -1028,6 +925,7 @@ template <int FID> static void eq_evals_t(Ctx& c, const void* r_host, uint32_t e
 template <int FID> static void eq_evals_pair_t(Ctx& c, const void* r_host, uint32_t ellL, uint32_t ellR, uint32_t flags, uint32_t* d_outL,
                                                uint32_t* d_outR) {
   using F = Fp<FID>;
+  challenges_in_range<FID>(r_host, ellL + ellR);
   if (ellL > EqDirectFn<FID>::kMaxEll || ellR > EqDirectFn<FID>::kMaxEll) {
     eq_evals_t<FID>(c, r_host, ellL, flags, d_outL);
     eq_evals_t<FID>(c, (const uint8_t*)r_host + 32 * (size_t)ellL, ellR, flags, d_outR);
@@ -1259,7 +1157,20 @@ static bool binv_levels(Ctx& c, DeviceBackend& be, const std::vector<size_t>& sz
     std::vector<H> e(nt), pre(nt);
     H acc = H::one();
     for (size_t i = 0; i < nt; i++) {
-      if (!F::words_lt_p(top + 8 * i)) throw Fail{NMX_E_SCALAR_RANGE, "batch_invert: element >= field modulus"};
+      // L == 0: the top level is the caller's own vector, whose words are any 256-bit values, read mod p as the device levels read
+      // them (2^256 < 6 p: at most five subtractions).  Above level 0 the words are chunk products stored through st(): canonical.
+      if (L == 0) {
+        while (!F::words_lt_p(top + 8 * i)) {
+          uint64_t bw = 0;
+          for (int j = 0; j < 8; j++) {
+            const uint64_t d = (uint64_t)top[8 * i + j] - FpParams<FID>::PW[j] - bw;
+            top[8 * i + j] = (uint32_t)d;
+            bw = (d >> 32) & 1u;
+          }
+        }
+      } else if (!F::words_lt_p(top + 8 * i)) {
+        throw Fail{NMX_E_SCALAR_RANGE, "batch_invert: a chunk product >= field modulus"};
+      }
       e[i] = H::from_canonical(top + 8 * i);  // the word as a plain value
       pre[i] = acc;
       acc = acc * e[i];

@@ -16,6 +16,7 @@
 #include "runtime.hpp"
 #include "host_fp4.hpp"
 #include "sumcheck_sums.hpp"  // ldw, eq_term and the lane bodies of the three sum passes
+#include "fieldvec_eval.hpp"  // eval_multi_lane: the lane body of k_eval_multi
 
 namespace nmx {
 
@@ -381,7 +382,7 @@ void fv_bind_eq_sums(Ctx& c, int field, int mode, const void* A, const void* B, 
 // is 3*ell launches each bound by a 64-step dependent chain; here a lane evaluates a 16-coefficient chunk at all m
 // points (coefficients read once), scales by u^(16 * lane) from a table, the block sums over its 256 chunks, and
 // thread 0 applies the block's own power u^(4096 * block).  A polynomial owns whole blocks.
-static constexpr uint32_t kEvalChunk = 16, kEvalMaxPts = 4;
+// (kEvalChunk, kEvalMaxPts and the lane body eval_multi_lane: fieldvec_eval.hpp)
 struct EvalPoly {
   const uint32_t* f;
   uint32_t len, first_block, nblocks;
@@ -409,18 +410,7 @@ __global__ __launch_bounds__(256) void k_eval_multi(const EvalPoly* polys, uint3
   for (uint32_t j = 0; j < kEvalMaxPts; j++) h[j] = F::zero();
   if (lo < P.len) {
     const uint32_t hi = lo + kEvalChunk < P.len ? lo + kEvalChunk : P.len;
-    F u[kEvalMaxPts];
-#pragma unroll
-    for (uint32_t j = 0; j < kEvalMaxPts; j++) u[j] = j < m ? ldw<FID>(pts, j) : F::zero();
-    for (uint32_t i = hi; i-- > lo;) {
-      const F c = ldw<FID>(P.f, i);
-#pragma unroll
-      for (uint32_t j = 0; j < kEvalMaxPts; j++)
-        if (j < m) h[j] = (c + u[j] * h[j]).norm();                    // < 2.1 p, normalized
-    }
-#pragma unroll
-    for (uint32_t j = 0; j < kEvalMaxPts; j++)
-      if (j < m) h[j] = (h[j] * ldw<FID>(pw16, (size_t)j * 256 + threadIdx.x)).canon();
+    eval_multi_lane<FID>(P.f, lo, hi, m, pts, pw16, threadIdx.x, h);
   }
 #pragma unroll  // (constant indices: h[] stays in registers -- as a rolled loop over j < m it lived in 160 B of scratch)
   for (uint32_t j = 0; j < kEvalMaxPts; j++) {
@@ -457,6 +447,11 @@ static void eval_multi_t(Ctx& c, const void* const* polys, const size_t* lens, s
                          uint32_t flags, uint8_t* out) {
   using F = Fp<FID>;
   const bool mont = flags & NMX_SCALARS_MONT, dev = flags & NMX_SCALARS_DEVICE;
+  for (size_t j = 0; j < m; j++) {  // a point >= p is NMX_E_SCALAR_RANGE before anything is staged or launched
+    uint32_t w[8];
+    memcpy(w, (const uint8_t*)points + 32 * j, 32);
+    require(F::words_lt_p(w), NMX_E_SCALAR_RANGE, "point >= field modulus");
+  }
   std::vector<EvalPoly> desc(k);
   uint32_t blocks = 0;
   size_t stage_bytes = 0;
@@ -492,7 +487,6 @@ static void eval_multi_t(Ctx& c, const void* const* polys, const size_t* lens, s
   std::vector<uint32_t> hpts(8 * m), h16(8 * 256 * m), h4096(8 * 20 * m);
   for (size_t j = 0; j < m; j++) {
     const uint8_t* pj = (const uint8_t*)points + 32 * j;
-    (void)challenge_internal<FID>(pj, mont);               // (the range check: a point >= p is NMX_E_SCALAR_RANGE)
     const H u = mont ? H::from_mont256(pj) : H::from_canonical(pj);
     u.to_device().to_words(hpts.data() + 8 * j);
     H u16 = u;

@@ -317,7 +317,9 @@ template <int FID, int MODE, bool QUAD = false> __global__ __launch_bounds__(256
       if (MODE >= 3) sc_bind2<FID>(a.B, a.oB, a.r, id, a.hq, b0, b1);
       if (MODE == 3) sc_bind2<FID>(a.C, a.oC, a.r, id, a.hq, c0, c1);
     } else {
-      a0 = ldw<FID>(a.A, id), a1 = ldw<FID>(a.A, (size_t)id + a.hq);
+      // (MODE 1 -- an evaluation runs it with hq == the polynomial's length -- uses no second half: nothing is read past a.A[hq))
+      a0 = ldw<FID>(a.A, id);
+      if (MODE != 1) a1 = ldw<FID>(a.A, (size_t)id + a.hq);
       if (MODE >= 3) b0 = ldw<FID>(a.B, id), b1 = ldw<FID>(a.B, (size_t)id + a.hq);
       if (MODE == 3) c0 = ldw<FID>(a.C, id);
     }
