@@ -698,6 +698,47 @@ int nmx_mercury_h_poly(int field_id, const void* f, size_t n_rows, size_t n_cols
  * of nmx_set_option sets the rows per segment (0 = by size) and never changes a result. */
 int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, size_t n_cols, const void* alpha,
                                    uint32_t flags, void* out_q /* (n_rows - 1) * n_cols */, void* out_g /* n_cols */);
+/* ---- NeutronNova's folding step (neutron::NIFS::prove, src/neutron/nifs.rs:200-289) ----------------------------------------------------
+ * The N-sized work of neutron::NIFS::prove that no other call expresses; its commitments are nmx_commit / nmx_msm_u64 and its two
+ * multiply_vec products nmx_spmv_apply_many.  Notation: for left, right >= 1, E is a vector of left + right elements,
+ * e = E[0, left) and f = E[left, left + right); an N-vector (N = left * right) is indexed k = i * left + j with i < right, j < left;
+ * X(t) = X1 + t (X2 - X1).  left and right need not be powers of two.
+ * Flags: NMX_SCALARS_MONT (every vector, challenge and output is in Montgomery limbs), NMX_SCALARS_DEVICE (EVERY vector pointer of the
+ * call is HBM; otherwise every vector is a host array staged through the context's workspace; mixed placement cannot be expressed),
+ * NMX_ASYNC where noted below (with HBM operands only, as for nmx_nifs_fold); any other flag: NMX_E_ARG.  The challenges tau, rho and r_b
+ * are always host pointers.  OPERAND WORDS above applies: a 32-byte word of an input vector is ANY 256-bit value w and is read as
+ * w mod p, every output word is canonical (< p, in the form of the inputs), and a challenge >= p is NMX_E_SCALAR_RANGE, found before
+ * anything is launched: nothing is written.  All argument checks run before a device is touched: a malformed call returns its code on a
+ * machine without a GPU and leaves the caller's buffers as they were.  The calls run on logical device 0, are thread-safe and are
+ * ordered behind the calling thread's NMX_ASYNC calls. */
+/* PowPolynomial::new(tau, ell).split_evals(left, right) (src/spartan/polys/power.rs:62-86): out has left + right elements,
+ *   out[j] = tau^j, j < left;      out[left + i] = (tau^left)^i, i < right            (0^0 = 1)
+ * right == 1 gives f = [1]; the reference would index out of bounds there (it writes evals[1] of a one-element vector).  One launch:
+ * the host computes the squarings tau^(2^b) and (tau^left)^(2^b) and every lane multiplies the ones its index's bits select.
+ * left == 0, right == 0 or left + right >= 2^31: NMX_E_ARG.  NMX_ASYNC applies with an HBM `out`. */
+int nmx_pow_split_evals(int field_id, const void* tau, size_t left, size_t right, uint32_t flags, void* out /* left + right */);
+/* NIFS::prove_helper (src/neutron/nifs.rs:29-186): the five evaluations of the zero-fold's round polynomial at t = 0, 2, 3, 4, 5, in
+ * that order, as five elements on the host:
+ *   out_t = c_t(rho) * sum_{i < right} f(t)[i] * sum_{j < left} e(t)[j] * (Az(t)[k] * Bz(t)[k] - Cz(t)[k])
+ *   c_t(rho) = (1 - rho) + t (2 rho - 1)            -- 1 - rho, 3 rho - 1, 5 rho - 2, 7 rho - 3, 9 rho - 4
+ * E1, E2: left + right elements; the six products: left * right elements.  Synchronous.  left == 0 or right == 0: NMX_E_ARG;
+ * left * right >= 2^31: NMX_E_TOO_LARGE.  The result is exact mod p and depends neither on the launch geometry nor on the option
+ * "neutron_max_blocks" of nmx_set_option (the largest grid of this call and the next: 0 = by size). */
+int nmx_neutron_fold_sums(int field_id, size_t left, size_t right, const void* E1, const void* Az1, const void* Bz1, const void* Cz1,
+                          const void* E2, const void* Az2, const void* Bz2, const void* Cz2, const void* rho, uint32_t flags,
+                          uint8_t* out160);
+/* The sum of Structure::is_sat (src/neutron/relation.rs:83-97): out = sum_{i < right} f[i] * sum_{j < left} e[j] * (Az[k] * Bz[k] - Cz[k]),
+ * one element on the host; the same kernel as nmx_neutron_fold_sums with one point and one instance.  The comparison with U.T and the two
+ * commitments of is_sat stay the caller's (nmx_commit).  Synchronous; limits as for nmx_neutron_fold_sums. */
+int nmx_neutron_relation_sum(int field_id, size_t left, size_t right, const void* E, const void* Az, const void* Bz, const void* Cz,
+                             uint32_t flags, uint8_t* out32);
+/* FoldedWitness::fold (src/neutron/relation.rs:131-156): w = w1 + r_b (w2 - w1) over n_w elements and e = e1 + r_b (e2 - e1) over n_e
+ * elements, both in ONE launch (as nmx_nifs_fold).  Either length may be 0; its pointers are then ignored.  Element-wise in-place use
+ * (w == w1 or w == w2, e == e1 or e == e2) is allowed; any other overlap of an output with a buffer of the call: NMX_E_ARG.
+ * n_w + n_e >= 2^31: NMX_E_TOO_LARGE.  NMX_ASYNC applies with HBM operands.  The scalars r_W, r_E, u, X, T_out and the two point
+ * combinations of FoldedInstance::fold are O(1) work and stay on the caller's side. */
+int nmx_neutron_fold_witness(int field_id, const void* w1, const void* w2, size_t n_w, const void* e1, const void* e2, size_t n_e,
+                             const void* r_b, uint32_t flags, void* w /* n_w */, void* e /* n_e */);
 /* EqPolynomial::evals_from_points (src/spartan/polys/eq.rs:54-73): out[2^ell] = eq(r, x) for x in {0,1}^ell, r[0] the
  * most significant variable.  r: ell x 32 bytes, host.  out: host, or HBM with NMX_SCALARS_DEVICE; every entry canonical, in the
  * layout `flags` names (Montgomery: eq * 2^256 mod p).  ell >= 31: NMX_E_ARG.  A coordinate r[i] >= p: NMX_E_SCALAR_RANGE, found
@@ -835,6 +876,8 @@ int nmx_set_window_bits(uint32_t c);
  * to the two-pass kernels: 0 = 2^22; tests set 1),
  * "mercury_seg_rows" (rows per segment of nmx_mercury_divide_by_binomial's kernels: 0 = by size; tests force the multi-segment path
  * at tiny shapes),
+ * "neutron_max_blocks" (the largest grid of nmx_neutron_fold_sums / nmx_neutron_relation_sum: 0 = by size, at most 2048; tests force a
+ * wave's loop over several tiles at tiny shapes; never changes a result),
  * "host_split" / "host_split_min_n" (an MSM with HOST scalars over at least host_split_min_n = 2^19 pairs of a key on one device is cut
  * into contiguous pieces (host_split = 255, the default: 2 / 3 / 4 pieces from 2^19 / 2^20 / 2^21 pairs; 2..16: that many) -- the
  * reference's own chunk + reduce decomposition, src/provider/msm.rs:564-574 -- so that piece i's scalars cross PCIe while piece

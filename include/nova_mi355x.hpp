@@ -585,6 +585,29 @@ inline Scalar mercury_quot_f(int field, const void* f, size_t n, const void* q, 
   // one-coefficient polynomial {out[0]} evaluated at 0 is out[0]
   return poly_eval_multi(field, {out}, {1}, {Scalar{}})[0];
 }
+// NeutronNova's folding step over HBM-resident vectors (neutron/nifs.rs:200-289).  E: left + right elements, the products
+// left * right; the scalars are in the layout of the vectors (mont: Montgomery limbs)
+inline void pow_split_evals(int field, const Scalar& tau, size_t left, size_t right, void* out, bool mont = false) {  // power.rs:62-86; out: left + right
+  check(nmx_pow_split_evals(field, tau.data(), left, right, kAsync | (mont ? NMX_SCALARS_MONT : 0u), out));
+}
+// prove_helper (nifs.rs:29-186): the evaluations at t = 0, 2, 3, 4, 5
+inline std::array<Scalar, 5> neutron_fold_sums(int field, size_t left, size_t right, const void* E1, const void* Az1, const void* Bz1, const void* Cz1,
+                                               const void* E2, const void* Az2, const void* Bz2, const void* Cz2, const Scalar& rho, bool mont = false) {
+  std::array<Scalar, 5> out;
+  check(nmx_neutron_fold_sums(field, left, right, E1, Az1, Bz1, Cz1, E2, Az2, Bz2, Cz2, rho.data(), kDev | (mont ? NMX_SCALARS_MONT : 0u), out[0].data()));
+  return out;
+}
+// the sum of Structure::is_sat (relation.rs:83-97); the comparison with U.T is the caller's
+inline Scalar neutron_relation_sum(int field, size_t left, size_t right, const void* E, const void* Az, const void* Bz, const void* Cz, bool mont = false) {
+  Scalar out;
+  check(nmx_neutron_relation_sum(field, left, right, E, Az, Bz, Cz, kDev | (mont ? NMX_SCALARS_MONT : 0u), out.data()));
+  return out;
+}
+// FoldedWitness::fold (relation.rs:131-156): w = w1 + r_b (w2 - w1), e = e1 + r_b (e2 - e1); w == w1 and e == e1 (in place) are allowed
+inline void neutron_fold_witness(int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* e2, size_t n_e, const Scalar& r_b,
+                                 void* w, void* e, bool mont = false) {
+  check(nmx_neutron_fold_witness(field, w1, w2, n_w, e1, e2, n_e, r_b.data(), kAsync | (mont ? NMX_SCALARS_MONT : 0u), w, e));
+}
 // ppsnark's evaluation_oracles (ppsnark.rs:220-253): out[i] = mem[addr[i]], addr n field elements whose values are the addresses; all in HBM
 inline void gather(int field, const void* mem, size_t n_mem, const void* addr, size_t n, void* out, bool mont = false) {
   check(nmx_field_gather(field, mem, n_mem, addr, n, kDev | (mont ? NMX_SCALARS_MONT : 0u), out));

@@ -103,6 +103,10 @@ def lib():
     L.nmx_poly_suffix_horner.argtypes = [i, vp, sz, vp, u32, vp]
     L.nmx_mercury_h_poly.argtypes = [i, vp, sz, sz, vp, u32, vp]
     L.nmx_mercury_divide_by_binomial.argtypes = [i, vp, sz, sz, vp, u32, vp, vp]
+    L.nmx_pow_split_evals.argtypes = [i, vp, sz, sz, u32, vp]
+    L.nmx_neutron_fold_sums.argtypes = [i, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
+    L.nmx_neutron_relation_sum.argtypes = [i, sz, sz, vp, vp, vp, vp, u32, vp]
+    L.nmx_neutron_fold_witness.argtypes = [i, vp, vp, sz, vp, vp, sz, vp, u32, vp, vp]
     L.nmx_eq_evals_from_points.argtypes = [i, vp, sz, u32, vp]
     L.nmx_mle_evaluate.argtypes = [i, vp, sz, vp, sz, u32, vp]
     L.nmx_spmv_register.argtypes = [i, vp, vp, vp, sz, sz, u32, ctypes.POINTER(u64)]

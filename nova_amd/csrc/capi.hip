@@ -2378,6 +2378,84 @@ int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, s
   });
 }
 
+// ---- NeutronNova's folding step (neutron.hpp; src/neutron/nifs.rs:29-186, src/neutron/relation.rs:83-97 and :131-156, power.rs:62-86) -----
+// Everything that can be refused is refused before a device is leased: a refused call needs no device, launches nothing, writes nothing.
+static void neutron_check_flags(int field_id, uint32_t flags, uint32_t allowed, const char* msg) {
+  require((flags & ~allowed) == 0, NMX_E_ARG, msg);
+  with_field(field_id, [](auto) {});
+}
+static void neutron_check_scalar(int field_id, const void* s, const char* msg) {
+  with_field(field_id, [&](auto F) {
+    uint32_t w[8];
+    memcpy(w, s, 32);
+    require(Fp<decltype(F)::value>::words_lt_p(w), NMX_E_SCALAR_RANGE, msg);
+  });
+}
+static void neutron_check_shape(size_t left, size_t right) {
+  require(left >= 1 && right >= 1, NMX_E_ARG, "nmx_neutron_*: left and right must be at least 1");
+  require(left < (1ull << 31) && right < (1ull << 31) && (uint64_t)left * (uint64_t)right < (1ull << 31), NMX_E_TOO_LARGE,
+          "nmx_neutron_*: left * right must stay below 2^31");
+}
+int nmx_pow_split_evals(int field_id, const void* tau, size_t left, size_t right, uint32_t flags, void* out) {
+  return guarded([&] {
+    neutron_check_flags(field_id, flags, NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_ASYNC,
+                        "nmx_pow_split_evals: only NMX_SCALARS_MONT, NMX_SCALARS_DEVICE and NMX_ASYNC apply");
+    require(tau && out, NMX_E_ARG, "null argument");
+    require(left >= 1 && right >= 1 && left < (1ull << 31) && right < (1ull << 31) && (uint64_t)left + (uint64_t)right < (1ull << 31), NMX_E_ARG,
+            "nmx_pow_split_evals: left and right must be at least 1 and left + right below 2^31");
+    neutron_check_scalar(field_id, tau, "nmx_pow_split_evals: tau >= field modulus");
+    CtxLease L;
+    fv_pow_split_evals(*L.c, field_id, tau, left, right, flags, out);
+  });
+}
+int nmx_neutron_fold_sums(int field_id, size_t left, size_t right, const void* E1, const void* Az1, const void* Bz1, const void* Cz1,
+                          const void* E2, const void* Az2, const void* Bz2, const void* Cz2, const void* rho, uint32_t flags, uint8_t* out160) {
+  return guarded([&] {
+    neutron_check_flags(field_id, flags, NMX_SCALARS_MONT | NMX_SCALARS_DEVICE, "nmx_neutron_fold_sums: only NMX_SCALARS_MONT and NMX_SCALARS_DEVICE apply");
+    require(E1 && Az1 && Bz1 && Cz1 && E2 && Az2 && Bz2 && Cz2 && rho && out160, NMX_E_ARG, "null argument");
+    neutron_check_shape(left, right);
+    neutron_check_scalar(field_id, rho, "nmx_neutron_fold_sums: rho >= field modulus");
+    const void* v[8] = {E1, Az1, Bz1, Cz1, E2, Az2, Bz2, Cz2};
+    CtxLease L;
+    uint8_t five[160] = {0};
+    fv_neutron_fold_sums(*L.c, field_id, left, right, v, rho, flags, five);
+    memcpy(out160, five, 160);
+  });
+}
+int nmx_neutron_relation_sum(int field_id, size_t left, size_t right, const void* E, const void* Az, const void* Bz, const void* Cz, uint32_t flags,
+                             uint8_t* out32) {
+  return guarded([&] {
+    neutron_check_flags(field_id, flags, NMX_SCALARS_MONT | NMX_SCALARS_DEVICE, "nmx_neutron_relation_sum: only NMX_SCALARS_MONT and NMX_SCALARS_DEVICE apply");
+    require(E && Az && Bz && Cz && out32, NMX_E_ARG, "null argument");
+    neutron_check_shape(left, right);
+    const void* v[4] = {E, Az, Bz, Cz};
+    CtxLease L;
+    uint8_t one[32] = {0};
+    fv_neutron_relation_sum(*L.c, field_id, left, right, v, flags, one);
+    memcpy(out32, one, 32);
+  });
+}
+int nmx_neutron_fold_witness(int field_id, const void* w1, const void* w2, size_t n_w, const void* e1, const void* e2, size_t n_e, const void* r_b,
+                             uint32_t flags, void* w, void* e) {
+  return guarded([&] {
+    neutron_check_flags(field_id, flags, NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_ASYNC,
+                        "nmx_neutron_fold_witness: only NMX_SCALARS_MONT, NMX_SCALARS_DEVICE and NMX_ASYNC apply");
+    require(((w1 && w2 && w) || n_w == 0) && ((e1 && e2 && e) || n_e == 0) && r_b, NMX_E_ARG, "null argument");
+    require(n_w < (1ull << 31) && n_e < (1ull << 31) && n_w + n_e < (1ull << 31), NMX_E_TOO_LARGE, "nmx_neutron_fold_witness: vectors too long");
+    // element-wise in place (an output that IS one of its own inputs) is fine: a lane reads its element before it writes it; any other overlap is not
+    const auto clash = [](const void* o, const void* in, size_t n, bool own) { return !(own && o == in) && mercury_overlap(o, n, in, n); };
+    require(!clash(w, w1, n_w, true) && !clash(w, w2, n_w, true) && !clash(e, e1, n_e, true) && !clash(e, e2, n_e, true) &&
+                !mercury_overlap(w, n_w, e, n_e) && !mercury_overlap(w, n_w, e1, n_e) && !mercury_overlap(w, n_w, e2, n_e) &&
+                !mercury_overlap(e, n_e, w1, n_w) && !mercury_overlap(e, n_e, w2, n_w),
+            NMX_E_ARG, "nmx_neutron_fold_witness: an output overlaps a buffer other than its own input");
+    neutron_check_scalar(field_id, r_b, "nmx_neutron_fold_witness: r_b >= field modulus");
+    if (n_w + n_e == 0) return;
+    CtxLease L;
+    fv_neutron_fold_witness(*L.c, field_id, n_w ? w1 : nullptr, n_w ? w2 : nullptr, n_w, n_e ? e1 : nullptr, n_e ? e2 : nullptr, n_e, r_b, flags,
+                            n_w ? w : nullptr, n_e ? e : nullptr);
+  });
+}
+
 int nmx_poly_eval_multi(int field, const void* const* polys, const size_t* lens, size_t k, const void* points, size_t m,
                         uint32_t flags, uint8_t* out) {
   return guarded([&] {
@@ -3360,6 +3438,7 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "horner_window") G.horner_window = value ? value : 64u;
     else if (n == "horner_sub") G.horner_sub = value;
     else if (n == "mercury_seg_rows") G.mercury_seg_rows = value;
+    else if (n == "neutron_max_blocks") G.neutron_max_blocks = value;
     else if (n == "eq_max_blocks") G.eq_max_blocks = value;
     else if (n == "horner_spin_limit") G.horner_spin_limit = value;
     else if (n == "seg_heavy_above") G.seg_heavy_above = value > 63u ? 63u : value;

@@ -333,6 +333,7 @@ struct Global {
   std::atomic<uint32_t> horner_spin_limit{0};     // option horner_spin_limit: polls before a wave of the scan gives up (0 = 2^22; tests set 1 to force the fall-back)
   std::atomic<uint32_t> horner_window{64};        // option horner_window: tiles per look-back round of the single-pass scan (tests: 1 .. 63 force the multi-round path)
   std::atomic<uint32_t> mercury_seg_rows{0};      // option mercury_seg_rows: rows per segment of Mercury's division kernels (mercury.hpp mercury_plan; 0 = by size; tests force the multi-segment path at tiny shapes)
+  std::atomic<uint32_t> neutron_max_blocks{0};    // option neutron_max_blocks: the largest grid of the two NeutronNova sums (neutron.hpp neutron_blocks; 0 = by size; tests force a wave's loop over tiles at tiny shapes)
   std::atomic<uint32_t> seg_heavy_above{0};       // env NMX_TUNE_SEG_HEAVY_ABOVE / option seg_heavy_above: 0 = by pieces per bucket (8 or 12)
   std::atomic<uint32_t> prefix_tables{2};         // env NMX_TUNE_PREFIX_TABLES / option prefix_tables: narrower table sets over a key's first points (capi.hip add_prefix_tables): 0 none, 1 the 2^18-point set of wide-table keys only, 2 the whole chain (batches descend it)
   std::atomic<uint32_t> no_batch_fuse{0};         // env NMX_TUNE_NO_BATCH_FUSE / option no_batch_fuse: every vector of a batch runs alone
@@ -800,6 +801,14 @@ bool fv_gather(Ctx&, int field, const void* mem, size_t n_mem, const void* addr,
 bool fv_ppsnark_mem_oracles(Ctx&, int field, size_t k, size_t n, const void* const* mem, const void* const* addr, const void* const* L,
                             const void* const* ts, const void* gamma, const void* r, uint32_t flags, void* const* out_t_plus_r,
                             void* const* out_w_plus_r, void* const* out_t_plus_r_inv, void* const* out_w_plus_r_inv);
+// NeutronNova's folding step (neutron.hpp): the pow tables, the five sums of prove_helper (v8: E1, Az1, Bz1, Cz1, E2, Az2, Bz2, Cz2), the sum
+// of is_sat (v4: E, Az, Bz, Cz) and the witness fold.  Vectors follow NMX_SCALARS_DEVICE, tau / rho / r_b are host pointers; the two sums are
+// synchronous, the other two take NMX_ASYNC with HBM operands.  Shapes, NULLs and the scalars' range are the caller's to check.
+void fv_pow_split_evals(Ctx&, int field, const void* tau, size_t left, size_t right, uint32_t flags, void* out);
+void fv_neutron_fold_sums(Ctx&, int field, size_t left, size_t right, const void* const* v8, const void* rho, uint32_t flags, uint8_t* out160);
+void fv_neutron_relation_sum(Ctx&, int field, size_t left, size_t right, const void* const* v4, uint32_t flags, uint8_t* out32);
+void fv_neutron_fold_witness(Ctx&, int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* e2, size_t n_e, const void* r_b,
+                             uint32_t flags, void* w, void* e);
 void fv_nifs_fold(Ctx&, int field, const void* w1, const void* w2, size_t n_w, const void* e1, const void* t, size_t n_e, const void* r,
                   uint32_t flags, void* w, void* e);
 void fv_eq_evals(Ctx&, int field, const void* r_host, uint32_t ell, uint32_t flags, uint32_t* d_out);

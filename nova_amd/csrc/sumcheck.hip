@@ -643,3 +643,4 @@ void fv_eq_sums(Ctx& c, int field, int mode, const void* A, const void* B, const
 #include "sumcheck_ppsnark.hpp"
 #include "ipa.hpp"
 #include "ipa_verify.hpp"
+#include "neutron.hpp"

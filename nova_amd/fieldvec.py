@@ -473,6 +473,67 @@ def mercury_quot_f(field, f, q, zeta_b_minus_alpha, zeta, mont=False):
     return out[1:], (out[0].cpu().numpy() if _is_device_tensor(out) else out[0]).tobytes()
 
 
+# ---- NeutronNova's folding step (src/neutron/nifs.rs:200-289): pow tables, the zero-fold's sums, the witness fold ---------------------
+def pow_split_evals(field, tau, left, right, mont=False, device=None, async_=False):
+    """PowPolynomial::new(tau, ell).split_evals(left, right) (power.rs:62-86): [tau^j, j < left] ++ [(tau^left)^i, i < right].  device: a
+    torch device for an HBM result (a CUDA tensor), None for a host array."""
+    tt = _chal(tau)
+    dev = device is not None
+    if dev:
+        import torch
+        out = torch.empty((left + right, 32), dtype=torch.uint8, device=device)
+        po = out.data_ptr()
+    else:
+        out = np.zeros((left + right, 32), dtype=np.uint8)
+        po = out.ctypes.data
+    _check(L.lib().nmx_pow_split_evals(field, tt.ctypes.data, left, right, _flags(dev, mont, async_), po))
+    return out
+
+
+def _neutron_vecs(left, right, vecs):
+    ps = [_vec(x) for x in vecs]
+    dev = ps[0][2]
+    assert all(q[2] == dev for q in ps), "every vector host or every vector HBM"
+    for k, q in enumerate(ps):
+        assert q[1] == (left + right if k % 4 == 0 else left * right), "E has left + right elements, Az / Bz / Cz left * right"
+    return ps, dev
+
+
+def neutron_fold_sums(field, left, right, E1, Az1, Bz1, Cz1, E2, Az2, Bz2, Cz2, rho, mont=False):
+    """NIFS::prove_helper (neutron/nifs.rs:29-186): the zero-fold's evaluations at t = 0, 2, 3, 4, 5 -> 160 bytes (five elements)."""
+    ps, dev = _neutron_vecs(left, right, (E1, Az1, Bz1, Cz1, E2, Az2, Bz2, Cz2))
+    rr = _chal(rho)
+    out = np.zeros(160, dtype=np.uint8)
+    _check(L.lib().nmx_neutron_fold_sums(field, left, right, *[q[0] for q in ps], rr.ctypes.data, _flags(dev, mont), out.ctypes.data))
+    return out.tobytes()
+
+
+def neutron_relation_sum(field, left, right, E, Az, Bz, Cz, mont=False):
+    """The sum of Structure::is_sat (neutron/relation.rs:83-97): sum_i f[i] sum_j e[j] (Az Bz - Cz)[i * left + j] -> 32 bytes."""
+    ps, dev = _neutron_vecs(left, right, (E, Az, Bz, Cz))
+    out = np.zeros(32, dtype=np.uint8)
+    _check(L.lib().nmx_neutron_relation_sum(field, left, right, *[q[0] for q in ps], _flags(dev, mont), out.ctypes.data))
+    return out.tobytes()
+
+
+def neutron_fold_witness(field, w1, w2, e1, e2, r_b, mont=False, async_=False, inplace=False):
+    """FoldedWitness::fold (neutron/relation.rs:131-156): (w1 + r_b (w2 - w1), e1 + r_b (e2 - e1)) in one launch.  inplace: the results
+    overwrite w1 and e1 (and are returned)."""
+    pw1, n_w, dev, k1 = _vec(w1)
+    pw2, n_w2, d2, _k2 = _vec(w2)
+    pe1, n_e, d3, k3 = _vec(e1)
+    pe2, n_e2, d4, _k4 = _vec(e2)
+    assert n_w == n_w2 and n_e == n_e2 and dev == d2 == d3 == d4, "w1 / w2 and e1 / e2 of equal lengths, all host or all HBM"
+    rr = _chal(r_b)
+    if inplace:
+        (pw, w), (pe, e) = (pw1, k1 if dev else k1.reshape(-1, 32)), (pe1, k3 if dev else k3.reshape(-1, 32))
+    else:
+        pw, w = _out_like(dev, n_w, w1)
+        pe, e = _out_like(dev, n_e, e1)
+    _check(L.lib().nmx_neutron_fold_witness(field, pw1, pw2, n_w, pe1, pe2, n_e, rr.ctypes.data, _flags(dev, mont, async_), pw, pe))
+    return w, e
+
+
 # ---- ppsnark's lookup gather and fused logUp oracles (src/spartan/ppsnark.rs:220-253, :371-489) ----------------------------------
 def gather(field, mem, addr, mont=False):
     """evaluation_oracles' L_row = eq[row], L_col = z[col] (ppsnark.rs:220-253): out[i] = mem[addr[i]].  addr holds FIELD ELEMENTS whose
