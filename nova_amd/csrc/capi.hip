@@ -2335,6 +2335,29 @@ int nmx_poly_suffix_horner(int field, const void* f, size_t n, const void* u, ui
   });
 }
 
+// ---- argument checks shared by the entry points below; all of them run before a device is leased --------------------------------------
+using ByteSpan = std::pair<uintptr_t, uintptr_t>;  // [first byte, one past the last) of a vector of 32-byte elements
+static ByteSpan span_of(const void* p, size_t elems) { return {(uintptr_t)p, (uintptr_t)p + elems * 32}; }
+static bool elems_overlap(const void* a, size_t a_elems, const void* b, size_t b_elems) {
+  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
+  return a_elems && b_elems && x < y + b_elems * 32 && y < x + a_elems * 32;
+}
+// no two of the spans share a byte (sorts them)
+static void require_disjoint(std::vector<ByteSpan>& spans, const char* msg) {
+  std::sort(spans.begin(), spans.end());
+  for (size_t i = 1; i < spans.size(); i++) require(spans[i - 1].second <= spans[i].first, NMX_E_ARG, msg);
+}
+// `count` scalars of 32 bytes at p, every one below the field's modulus
+static void require_canonical(int field_id, const void* p, size_t count, const char* msg) {
+  with_field(field_id, [&](auto F) {
+    for (size_t i = 0; i < count; i++) {
+      uint32_t w[8];
+      memcpy(w, (const uint8_t*)p + 32 * i, 32);
+      require(Fp<decltype(F)::value>::words_lt_p(w), NMX_E_SCALAR_RANGE, msg);
+    }
+  });
+}
+
 // ---- Mercury's prover passes (mercury.hpp; src/provider/mercury.rs:369-386 and :319-356) ----------------------------------------------
 // Everything that can be refused is refused before a device is leased: a refused call needs no device, launches nothing, writes nothing.
 static size_t mercury_check_shape(int field_id, size_t n_rows, size_t n_cols, uint32_t flags) {
@@ -2346,15 +2369,11 @@ static size_t mercury_check_shape(int field_id, size_t n_rows, size_t n_cols, ui
           "nmx_mercury_*: n_rows * n_cols must stay below 2^32");
   return n_rows * n_cols;
 }
-static bool mercury_overlap(const void* a, size_t a_elems, const void* b, size_t b_elems) {
-  const uintptr_t x = (uintptr_t)a, y = (uintptr_t)b;
-  return a_elems && b_elems && x < y + b_elems * 32 && y < x + a_elems * 32;
-}
 int nmx_mercury_h_poly(int field_id, const void* f, size_t n_rows, size_t n_cols, const void* eq_col, uint32_t flags, void* out_h) {
   return guarded([&] {
     const size_t n = mercury_check_shape(field_id, n_rows, n_cols, flags);
     require(f && eq_col && out_h, NMX_E_ARG, "null argument");
-    require(!mercury_overlap(out_h, n_rows, f, n) && !mercury_overlap(out_h, n_rows, eq_col, n_cols), NMX_E_ARG,
+    require(!elems_overlap(out_h, n_rows, f, n) && !elems_overlap(out_h, n_rows, eq_col, n_cols), NMX_E_ARG,
             "nmx_mercury_h_poly: out_h overlaps f or eq_col");
     CtxLease L;
     fv_mercury_h_poly(*L.c, field_id, f, n_rows, n_cols, eq_col, flags, out_h);
@@ -2366,13 +2385,9 @@ int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, s
     const size_t n = mercury_check_shape(field_id, n_rows, n_cols, flags), nq = n - n_cols;
     require(f && alpha && out_g && (out_q || n_rows == 1), NMX_E_ARG, "null argument");
     // never in place: every q element depends on rows that other waves still read, and the second walk re-reads f after q was written
-    require(!mercury_overlap(out_q, nq, f, n) && !mercury_overlap(out_g, n_cols, f, n) && !mercury_overlap(out_q, nq, out_g, n_cols),
+    require(!elems_overlap(out_q, nq, f, n) && !elems_overlap(out_g, n_cols, f, n) && !elems_overlap(out_q, nq, out_g, n_cols),
             NMX_E_ARG, "nmx_mercury_divide_by_binomial: out_q / out_g overlap f or each other");
-    with_field(field_id, [&](auto F) {
-      uint32_t w[8];
-      memcpy(w, alpha, 32);
-      require(Fp<decltype(F)::value>::words_lt_p(w), NMX_E_SCALAR_RANGE, "nmx_mercury_divide_by_binomial: alpha >= field modulus");
-    });
+    require_canonical(field_id, alpha, 1, "nmx_mercury_divide_by_binomial: alpha >= field modulus");
     CtxLease L;
     fv_mercury_divide_by_binomial(*L.c, field_id, f, n_rows, n_cols, alpha, flags, out_q, out_g);
   });
@@ -2383,13 +2398,6 @@ int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, s
 static void neutron_check_flags(int field_id, uint32_t flags, uint32_t allowed, const char* msg) {
   require((flags & ~allowed) == 0, NMX_E_ARG, msg);
   with_field(field_id, [](auto) {});
-}
-static void neutron_check_scalar(int field_id, const void* s, const char* msg) {
-  with_field(field_id, [&](auto F) {
-    uint32_t w[8];
-    memcpy(w, s, 32);
-    require(Fp<decltype(F)::value>::words_lt_p(w), NMX_E_SCALAR_RANGE, msg);
-  });
 }
 static void neutron_check_shape(size_t left, size_t right) {
   require(left >= 1 && right >= 1, NMX_E_ARG, "nmx_neutron_*: left and right must be at least 1");
@@ -2403,7 +2411,7 @@ int nmx_pow_split_evals(int field_id, const void* tau, size_t left, size_t right
     require(tau && out, NMX_E_ARG, "null argument");
     require(left >= 1 && right >= 1 && left < (1ull << 31) && right < (1ull << 31) && (uint64_t)left + (uint64_t)right < (1ull << 31), NMX_E_ARG,
             "nmx_pow_split_evals: left and right must be at least 1 and left + right below 2^31");
-    neutron_check_scalar(field_id, tau, "nmx_pow_split_evals: tau >= field modulus");
+    require_canonical(field_id, tau, 1, "nmx_pow_split_evals: tau >= field modulus");
     CtxLease L;
     fv_pow_split_evals(*L.c, field_id, tau, left, right, flags, out);
   });
@@ -2414,7 +2422,7 @@ int nmx_neutron_fold_sums(int field_id, size_t left, size_t right, const void* E
     neutron_check_flags(field_id, flags, NMX_SCALARS_MONT | NMX_SCALARS_DEVICE, "nmx_neutron_fold_sums: only NMX_SCALARS_MONT and NMX_SCALARS_DEVICE apply");
     require(E1 && Az1 && Bz1 && Cz1 && E2 && Az2 && Bz2 && Cz2 && rho && out160, NMX_E_ARG, "null argument");
     neutron_check_shape(left, right);
-    neutron_check_scalar(field_id, rho, "nmx_neutron_fold_sums: rho >= field modulus");
+    require_canonical(field_id, rho, 1, "nmx_neutron_fold_sums: rho >= field modulus");
     const void* v[8] = {E1, Az1, Bz1, Cz1, E2, Az2, Bz2, Cz2};
     CtxLease L;
     uint8_t five[160] = {0};
@@ -2443,12 +2451,12 @@ int nmx_neutron_fold_witness(int field_id, const void* w1, const void* w2, size_
     require(((w1 && w2 && w) || n_w == 0) && ((e1 && e2 && e) || n_e == 0) && r_b, NMX_E_ARG, "null argument");
     require(n_w < (1ull << 31) && n_e < (1ull << 31) && n_w + n_e < (1ull << 31), NMX_E_TOO_LARGE, "nmx_neutron_fold_witness: vectors too long");
     // element-wise in place (an output that IS one of its own inputs) is fine: a lane reads its element before it writes it; any other overlap is not
-    const auto clash = [](const void* o, const void* in, size_t n, bool own) { return !(own && o == in) && mercury_overlap(o, n, in, n); };
+    const auto clash = [](const void* o, const void* in, size_t n, bool own) { return !(own && o == in) && elems_overlap(o, n, in, n); };
     require(!clash(w, w1, n_w, true) && !clash(w, w2, n_w, true) && !clash(e, e1, n_e, true) && !clash(e, e2, n_e, true) &&
-                !mercury_overlap(w, n_w, e, n_e) && !mercury_overlap(w, n_w, e1, n_e) && !mercury_overlap(w, n_w, e2, n_e) &&
-                !mercury_overlap(e, n_e, w1, n_w) && !mercury_overlap(e, n_e, w2, n_w),
+                !elems_overlap(w, n_w, e, n_e) && !elems_overlap(w, n_w, e1, n_e) && !elems_overlap(w, n_w, e2, n_e) &&
+                !elems_overlap(e, n_e, w1, n_w) && !elems_overlap(e, n_e, w2, n_w),
             NMX_E_ARG, "nmx_neutron_fold_witness: an output overlaps a buffer other than its own input");
-    neutron_check_scalar(field_id, r_b, "nmx_neutron_fold_witness: r_b >= field modulus");
+    require_canonical(field_id, r_b, 1, "nmx_neutron_fold_witness: r_b >= field modulus");
     if (n_w + n_e == 0) return;
     CtxLease L;
     fv_neutron_fold_witness(*L.c, field_id, n_w ? w1 : nullptr, n_w ? w2 : nullptr, n_w, n_e ? e1 : nullptr, n_e ? e2 : nullptr, n_e, r_b, flags,
@@ -2812,6 +2820,12 @@ struct ScStaged {
     HIPCHK(hipMemcpyAsync(d, host, elems * 32, hipMemcpyHostToDevice, c.stream));
     return d;
   }
+  // uploads `count` host tables, table i of elems(i) elements; returns their device pointers in order (valid until the next upload)
+  void* const* up_list(Ctx& c, void* const* host, size_t count, const std::function<size_t(size_t)>& elems) {
+    const size_t at = dev.size();
+    for (size_t i = 0; i < count; i++) up(c, host[i], elems(i));
+    return dev.data() + at;
+  }
 };
 int nmx_sumcheck_prove_cubic_with_three_inputs(int field, const void* claim, const void* taus, size_t num_rounds, void* A, void* B, void* C,
                                                uint32_t flags, nmx_transcript_fn transcript, void* ctx, uint8_t* out_polys, uint8_t* out_r,
@@ -2853,10 +2867,8 @@ int nmx_sumcheck_prove_batch_eval(int field, const void* claims, const size_t* n
     for (size_t i = 0; i < k; i++) require(polys[i] && eq_points[i] && num_rounds[i] < 31, NMX_E_ARG, "null polynomial / evaluation point");
     CtxLease L;
     ScStaged st;
-    std::vector<void*> staged;
     if (!(flags & NMX_SCALARS_DEVICE)) {
-      for (size_t i = 0; i < k; i++) staged.push_back(st.up(*L.c, polys[i], (size_t)1 << num_rounds[i]));
-      polys = staged.data();
+      polys = st.up_list(*L.c, polys, k, [&](size_t i) { return (size_t)1 << num_rounds[i]; });
       flags |= NMX_SCALARS_DEVICE;
     }
     fv_sumcheck_prove_batch(*L.c, field, (const uint8_t*)claims, num_rounds, polys, (const uint8_t* const*)eq_points, (const uint8_t*)coeffs, k,
@@ -2872,37 +2884,23 @@ int nmx_sumcheck_prove_batched_cubic(int field_id, const void* claim, const void
     check_sc_args(field_id, num_rounds, flags, transcript);
     require(k >= 1 && k <= 16, NMX_E_ARG, "prove_batched_cubic: between 1 and 16 triples");
     require(claim && (taus || num_rounds == 0) && As && Bs && Cs && alphas, NMX_E_ARG, "null argument");
-    const size_t n = (size_t)1 << num_rounds, bytes = n * 32;
-    std::vector<std::pair<uintptr_t, uintptr_t>> span;
+    const size_t n = (size_t)1 << num_rounds;
+    std::vector<ByteSpan> span;
     for (size_t i = 0; i < k; i++)
       for (void* const* T : {As, Bs, Cs}) {
         require(T[i] != nullptr, NMX_E_ARG, "prove_batched_cubic: null table");
-        span.emplace_back((uintptr_t)T[i], (uintptr_t)T[i] + bytes);
+        span.push_back(span_of(T[i], n));
       }
-    std::sort(span.begin(), span.end());
-    for (size_t i = 1; i < span.size(); i++)
-      require(span[i - 1].second <= span[i].first, NMX_E_ARG, "prove_batched_cubic: two tables overlap (they are bound in place)");
-    with_field(field_id, [&](auto F) {
-      using Field = Fp<decltype(F)::value>;
-      auto lt_p = [](const void* p, size_t i) {
-        uint32_t w[8];
-        memcpy(w, (const uint8_t*)p + 32 * i, 32);
-        return Field::words_lt_p(w);
-      };
-      bool ok = lt_p(claim, 0);
-      for (size_t i = 0; i < num_rounds; i++) ok = ok && lt_p(taus, i);
-      for (size_t i = 0; i < k; i++) ok = ok && lt_p(alphas, i);
-      require(ok, NMX_E_SCALAR_RANGE, "prove_batched_cubic: claim / tau / alpha >= field modulus");
-    });
+    require_disjoint(span, "prove_batched_cubic: two tables overlap (they are bound in place)");
+    const char* range_msg = "prove_batched_cubic: claim / tau / alpha >= field modulus";
+    require_canonical(field_id, claim, 1, range_msg), require_canonical(field_id, taus, num_rounds, range_msg), require_canonical(field_id, alphas, k, range_msg);
     // (k and the scalars are checked again below the lease -- fv_sumcheck_prove_batched_cubic's require, ScAlg::in -- on purpose: those layers
     // do not rely on their caller; the checks here are what makes a refused call need no device and launch nothing)
     CtxLease L;
     ScStaged st;
-    std::vector<void*> staged;
     if (!(flags & NMX_SCALARS_DEVICE)) {
-      for (void* const* T : {As, Bs, Cs})
-        for (size_t i = 0; i < k; i++) staged.push_back(st.up(*L.c, T[i], n));
-      As = staged.data(), Bs = staged.data() + k, Cs = staged.data() + 2 * k;
+      for (void* const* T : {As, Bs, Cs}) st.up_list(*L.c, T, k, [n](size_t) { return n; });
+      As = st.dev.data(), Bs = As + k, Cs = Bs + k;
       flags |= NMX_SCALARS_DEVICE;
     }
     fv_sumcheck_prove_batched_cubic(*L.c, field_id, claim, taus, num_rounds, As, Bs, Cs, alphas, k, flags, transcript, ctx, out_polys, out_r, out_claims);
@@ -2917,33 +2915,20 @@ int nmx_sumcheck_prove_ppsnark(int field_id, size_t num_rounds, void* const* tab
     check_sc_args(field_id, num_rounds, flags, transcript);
     require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE)) == 0, NMX_E_ARG, "prove_ppsnark: unknown flag");
     require(tables && (rhos || num_rounds == 0) && (r_outer || num_rounds == 0) && claims2 && coeffs9, NMX_E_ARG, "null argument");
-    const size_t n = (size_t)1 << num_rounds, bytes = n * 32;
-    std::vector<std::pair<uintptr_t, uintptr_t>> span;
+    const size_t n = (size_t)1 << num_rounds;
+    std::vector<ByteSpan> span;
     for (size_t t = 0; t < NMX_PPS_TABLES; t++) {
       require(tables[t] != nullptr, NMX_E_ARG, "prove_ppsnark: null table");
-      span.emplace_back((uintptr_t)tables[t], (uintptr_t)tables[t] + bytes);
+      span.push_back(span_of(tables[t], n));
     }
-    std::sort(span.begin(), span.end());
-    for (size_t i = 1; i < span.size(); i++)
-      require(span[i - 1].second <= span[i].first, NMX_E_ARG, "prove_ppsnark: two tables overlap (they are bound in place)");
-    with_field(field_id, [&](auto F) {
-      using Field = Fp<decltype(F)::value>;
-      auto lt_p = [](const void* p, size_t i) {
-        uint32_t w[8];
-        memcpy(w, (const uint8_t*)p + 32 * i, 32);
-        return Field::words_lt_p(w);
-      };
-      bool ok = lt_p(claims2, 0) && lt_p(claims2, 1);
-      for (size_t i = 0; i < num_rounds; i++) ok = ok && lt_p(rhos, i) && lt_p(r_outer, i);
-      for (size_t i = 0; i < 9; i++) ok = ok && lt_p(coeffs9, i);
-      require(ok, NMX_E_SCALAR_RANGE, "prove_ppsnark: rho / r_outer / claim / coefficient >= field modulus");
-    });
+    require_disjoint(span, "prove_ppsnark: two tables overlap (they are bound in place)");
+    const char* range_msg = "prove_ppsnark: rho / r_outer / claim / coefficient >= field modulus";
+    require_canonical(field_id, claims2, 2, range_msg), require_canonical(field_id, rhos, num_rounds, range_msg);
+    require_canonical(field_id, r_outer, num_rounds, range_msg), require_canonical(field_id, coeffs9, 9, range_msg);
     CtxLease L;
     ScStaged st;
-    std::vector<void*> staged;
     if (!(flags & NMX_SCALARS_DEVICE)) {
-      for (size_t t = 0; t < NMX_PPS_TABLES; t++) staged.push_back(st.up(*L.c, tables[t], n));
-      tables = staged.data();
+      tables = st.up_list(*L.c, tables, NMX_PPS_TABLES, [n](size_t) { return n; });
       flags |= NMX_SCALARS_DEVICE;
     }
     fv_sumcheck_prove_ppsnark(*L.c, field_id, num_rounds, tables, rhos, r_outer, claims2, coeffs9, flags, transcript, ctx, out_polys, out_r, out_finals);
@@ -2960,7 +2945,7 @@ int nmx_field_gather(int field_id, const void* mem, size_t n_mem, const void* ad
     require((mem && addr && out) || n == 0, NMX_E_ARG, "null argument");
     require(n_mem > 0 || n == 0, NMX_E_ARG, "nmx_field_gather: n_mem == 0 with n > 0");
     require(n < (1ull << 32) && n_mem < (1ull << 32), NMX_E_TOO_LARGE, "nmx_field_gather: n and n_mem must stay below 2^32");
-    require(!mercury_overlap(out, n, mem, n_mem) && !mercury_overlap(out, n, addr, n), NMX_E_ARG, "nmx_field_gather: out overlaps mem or addr");
+    require(!elems_overlap(out, n, mem, n_mem) && !elems_overlap(out, n, addr, n), NMX_E_ARG, "nmx_field_gather: out overlaps mem or addr");
     if (n == 0) return;
     CtxLease L;
     if (!fv_gather(*L.c, field_id, mem, n_mem, addr, n, flags, out))
@@ -2978,28 +2963,20 @@ int nmx_ppsnark_mem_oracles(int field_id, size_t k, size_t n, const void* const*
     require(k >= 1 && k <= 8, NMX_E_ARG, "nmx_ppsnark_mem_oracles: k must be 1 .. 8");
     require(n >= 1, NMX_E_ARG, "nmx_ppsnark_mem_oracles: n must be at least 1");
     require(n < (1ull << 32) && 2 * (uint64_t)k * (uint64_t)n < (1ull << 32), NMX_E_TOO_LARGE, "nmx_ppsnark_mem_oracles: 2 k n must stay below 2^32");
-    std::vector<std::pair<uintptr_t, uintptr_t>> ins, outs;
+    std::vector<ByteSpan> ins, outs;
     for (size_t m = 0; m < k; m++) {
       for (const void* p : {mem[m], addr[m], L_[m], ts[m]}) {
         require(p != nullptr, NMX_E_ARG, "nmx_ppsnark_mem_oracles: null vector");
-        ins.emplace_back((uintptr_t)p, (uintptr_t)p + n * 32);
+        ins.push_back(span_of(p, n));
       }
       for (void* p : {out_t_plus_r[m], out_w_plus_r[m], out_t_plus_r_inv[m], out_w_plus_r_inv[m]}) {
         require(p != nullptr, NMX_E_ARG, "nmx_ppsnark_mem_oracles: null vector");
-        outs.emplace_back((uintptr_t)p, (uintptr_t)p + n * 32);
+        outs.push_back(span_of(p, n));
       }
     }
-    with_field(field_id, [&](auto F) {
-      uint32_t w[8];
-      for (const void* s : {gamma, r}) {
-        memcpy(w, s, 32);
-        require(Fp<decltype(F)::value>::words_lt_p(w), NMX_E_SCALAR_RANGE, "nmx_ppsnark_mem_oracles: gamma or r >= field modulus");
-      }
-    });
+    for (const void* s : {gamma, r}) require_canonical(field_id, s, 1, "nmx_ppsnark_mem_oracles: gamma or r >= field modulus");
     // inputs may alias one another (they are only read); an output may touch neither an input nor another output
-    std::sort(outs.begin(), outs.end());
-    for (size_t i = 1; i < outs.size(); i++)
-      require(outs[i - 1].second <= outs[i].first, NMX_E_ARG, "nmx_ppsnark_mem_oracles: two outputs overlap");
+    require_disjoint(outs, "nmx_ppsnark_mem_oracles: two outputs overlap");
     for (const auto& o : outs)
       for (const auto& in : ins)
         require(!(o.first < in.second && in.first < o.second), NMX_E_ARG, "nmx_ppsnark_mem_oracles: an output overlaps an input");

@@ -279,9 +279,7 @@ static void neutron_sums_t(Ctx& c, size_t left, size_t right, const void* const*
   NeutronArena ws{c, dev};
   uint32_t* partial = (uint32_t*)ws.take((size_t)blocks * 256);
   uint32_t* dout = (uint32_t*)ws.take(256);
-  F fm = F::zero();  // the form factor as a plain integer
-  if (mont) fm = pow2_plain<FID>(256);
-  else fm.l[0] = 1;
+  const F fm = sc_form_factor<FID>(mont);
   NeutronSumArgs<FID> a;
   const uint32_t* d[8] = {};
   const bool prof = G.profiling;
@@ -367,9 +365,7 @@ static void neutron_pow_t(Ctx& c, const void* tau, size_t left, size_t right, ui
     f.sq_f[b] = tl.to_device();
     tl = tl * tl;
   }
-  f.unit = F::zero();
-  if (mont) f.unit = pow2_plain<FID>(256);
-  else f.unit.l[0] = 1;
+  f.unit = sc_form_factor<FID>(mont);
   f.left = (uint32_t)left;
   arena_reserve(c, (dev ? 0 : pad256(n * 32)) + 256);
   NeutronArena ws{c, dev};

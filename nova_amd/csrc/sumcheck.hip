@@ -196,6 +196,13 @@ template <int FID> static Fp<FID> pow2_plain(uint32_t e) {
   }
   return acc.to_canonical();
 }
+// the vectors' form factor Fm as a plain integer in limbs (host): 1 (canonical) or 2^256 (Montgomery)
+template <int FID> static Fp<FID> sc_form_factor(bool mont) {
+  if (mont) return pow2_plain<FID>(256);
+  Fp<FID> one = Fp<FID>::zero();
+  one.l[0] = 1;
+  return one;
+}
 
 template <int FID, int MODE>
 static void eq_sums_t(Ctx& c, const void* A, const void* B, const void* C, size_t len, const void* eqL, size_t nL,
@@ -236,8 +243,7 @@ static void eq_sums_t(Ctx& c, const void* A, const void* B, const void* C, size_
   // constant 1 * Fm^2 / R' directly.
   F fconst = F::zero();
   if (MODE == 3) {
-    if (mont) fconst = pow2_plain<FID>(256);
-    else fconst.l[0] = 1;
+    fconst = sc_form_factor<FID>(mont);
   } else if (MODE == 2) {
     F one_plain = F::zero();
     one_plain.l[0] = 1;
@@ -328,8 +334,7 @@ static void bind_eq_sums_t(Ctx& c, const void* A, const void* B, const void* C, 
   uint32_t* dout = (uint32_t*)(c.arena + pad256((size_t)blocks * 64));
   F fconst = F::zero();
   if (MODE == 3) {
-    if (mont) fconst = pow2_plain<FID>(256);
-    else fconst.l[0] = 1;
+    fconst = sc_form_factor<FID>(mont);
   } else if (MODE == 2) {
     F one_plain = F::zero();
     one_plain.l[0] = 1;
@@ -639,6 +644,7 @@ void fv_eq_sums(Ctx& c, int field, int mode, const void* A, const void* B, const
 }  // namespace nmx
 
 #include "sumcheck_prove.hpp"
+#include "sumcheck_inplace.hpp"
 #include "sumcheck_batched.hpp"
 #include "sumcheck_ppsnark.hpp"
 #include "ipa.hpp"

@@ -1,5 +1,5 @@
 // sumcheck_ppsnark.hpp -- ppsnark's batched inner sum-check as ONE C call (nmx_sumcheck_prove_ppsnark).  Included by sumcheck.hip
-// behind sumcheck_batched.hpp; the mailbox, the eq heaps and the host algebra are sumcheck_prove.hpp's and sc_host.hpp's.
+// behind sumcheck_inplace.hpp, whose passes, kernel, hand-over and round loop it fills in; the host algebra is sc_host.hpp's ScPps.
 //
 //   RelaxedR1CSSNARK::prove_helper                                     src/spartan/ppsnark.rs:886-983
 //   MemorySumcheckInstance (claims 0-5, ten tables)                    src/spartan/ppsnark.rs:520-670
@@ -17,17 +17,9 @@
 //   inner group    4 tables (L_row, L_col, val, E), 4 sums (slot 2): sum a b c, sum da db dc, sum a(-1) b(-1) c(-1) without an eq factor;
 //                  t(0) of E under eq(r_outer)
 //   witness group  2 tables (W, masked_eq), 2 sums (slot 3): sum A B, sum A(-1) B(-1)
-// Three pass kinds per group, one index per lane, each index visited once:
-//   sums         id in [0, len/2) over the tables as they are: round 1.  Pointed at the HIGH halves with with_inf = 0 it gives t(1) of
-//                the claims under an eq whose tau is zero (t(0)'s summand alone, reading X[id] only): the fallback's third sum,
-//                t(-1) = 2 t(inf) + 2 t(0) - t(1), or 2 t(0) - t(1) for E.  (The witness group has no eq and no such form.)
-//   bind + sums  id in [0, len/4): every table of the group bound with the round's challenge in place (four loads, two stores per
-//                table: a lane reads exactly the elements it overwrites) and the NEXT round's sums over the bound values.
-//   bind only    id in [0, len/2): the last device bind, ONE kernel over all 16 tables (two loads, one store per table, no sums);
-//                the bound tables also go to a contiguous staging area which one stream-ordered copy brings to the host.
-// Each pass leaves its sums per block in the group's partials area; k_sum_partials_mail (one block) adds them into the group's
-// mailbox slot.  Every kernel is launched after its challenge exists and ends on its own: no pre-launched pass, no resident kernel,
-// nothing on the device waits for the host.  Of the sc_* options only sc_host_tail and sc_poll_us apply.
+// Three pass kinds (sumcheck_inplace.hpp) per group.  The sums pass pointed at the HIGH halves with with_inf = 0 gives t(1) of the claims
+// under an eq whose tau is zero (t(0)'s summand alone, reading X[id] only): the fallback's third sum, t(-1) = 2 t(inf) + 2 t(0) - t(1), or
+// 2 t(0) - t(1) for E.  (The witness group has no eq and no such form.)  The last device bind is ONE kernel over all 16 tables.
 //
 // Bytes per index (32 B elements).  bind + sums: memory 5 x (4 loads + 2 stores) = 960 B, inner 768 B, witness 384 B, plus the eq
 // reads (32 B, 64 B in the first half of the rounds) in the memory and inner groups: ~3.2 KB per index of len/4 for all four passes.
@@ -45,8 +37,7 @@
 //   A B            a * b                                              x Fm^2 / R'      2 factors
 #pragma once
 
-#include "msm_partition.hpp"  // NMX_DEV, NMX_TID: the device / emulation spellings
-#include "spmv_row.hpp"       // ld
+#include "sumcheck_inplace.hpp"
 
 namespace nmx {
 
@@ -78,23 +69,6 @@ template <int FID> struct ScPpsBindArgs {
   uint32_t n;       // len / 2
   uint32_t bind;    // 0: the tables go to the staging area as they are
 };
-
-template <int FID> NMX_DEV Fp<FID> sc_pps_factor(const uint32_t* eqL, const uint32_t* eqR, uint32_t shift, uint32_t mask, uint32_t id) {
-  Fp<FID> fac = ld<FID>(eqR, eqL ? (id & mask) : id);
-  if (eqL) fac = ld<FID>(eqL, id >> shift) * fac;  // < 1.01 p
-  return fac;
-}
-// bind_poly_var_top (multilinear.rs:65-84) on the two elements of X that next-round index id reads: lo + r (hi - lo), in place.
-// y0, y1 canonical.
-template <int FID> NMX_DEV void sc_pps_bind2(uint32_t* X, const Fp<FID>& r, uint32_t id, uint32_t hq, Fp<FID>& y0, Fp<FID>& y1) {
-  using F = Fp<FID>;
-  const F x00 = ld<FID>(X, id), x01 = ld<FID>(X, (size_t)id + hq);
-  const F x10 = ld<FID>(X, (size_t)id + 2 * (size_t)hq), x11 = ld<FID>(X, (size_t)id + 3 * (size_t)hq);
-  y0 = (x00 + r * F::sub2(x10, x00).norm()).norm().canon();
-  y1 = (x01 + r * F::sub2(x11, x01).norm()).norm().canon();
-  y0.to_words(X + 8 * (size_t)id);
-  y1.to_words(X + 8 * ((size_t)id + hq));
-}
 
 // Lazy-addition bounds shared by the three accumulator sets below.  Table elements and bound values are canonical (< p, limbs
 // < 2^29).  Every term added to an eq-free or eq-factored product sum is ONE product, normalised (limbs < 2^29) and < 1.05 p:
@@ -152,7 +126,7 @@ template <int FID> NMX_DEV void sc_pps_mem_sums_lane(const ScPpsMemArgs<FID>& a,
       const size_t hi = (size_t)id + a.n;
       t1 = ld<FID>(a.t, hi), ti1 = ld<FID>(a.tinv, hi), w1 = ld<FID>(a.w, hi), wi1 = ld<FID>(a.winv, hi);
     }
-    acc.add(a, sc_pps_factor<FID>(a.eqL, a.eqR, a.shift, a.mask, id), wi, t0, t1, ti0, ti1, w0, w1, wi0, wi1, ts0);
+    acc.add(a, sc_eq_factor<FID>(a.eqL, a.eqR, a.shift, a.mask, id), wi, t0, t1, ti0, ti1, w0, w1, wi0, wi1, ts0);
   }
   acc.flush();
 }
@@ -162,12 +136,12 @@ template <int FID> NMX_DEV void sc_pps_mem_bind_lane(const ScPpsMemArgs<FID>& a,
   for (uint64_t i64 = first; i64 < a.n; i64 += stride) {
     const uint32_t id = (uint32_t)i64;
     F t0, t1, ti0, ti1, w0, w1, wi0, wi1, ts0, ts1;
-    sc_pps_bind2<FID>(a.t, a.r, id, a.n, t0, t1);
-    sc_pps_bind2<FID>(a.tinv, a.r, id, a.n, ti0, ti1);
-    sc_pps_bind2<FID>(a.w, a.r, id, a.n, w0, w1);
-    sc_pps_bind2<FID>(a.winv, a.r, id, a.n, wi0, wi1);
-    sc_pps_bind2<FID>(a.ts, a.r, id, a.n, ts0, ts1);
-    acc.add(a, sc_pps_factor<FID>(a.eqL, a.eqR, a.shift, a.mask, id), true, t0, t1, ti0, ti1, w0, w1, wi0, wi1, ts0);
+    sc_bind2<FID>(a.t, a.r, id, a.n, t0, t1);
+    sc_bind2<FID>(a.tinv, a.r, id, a.n, ti0, ti1);
+    sc_bind2<FID>(a.w, a.r, id, a.n, w0, w1);
+    sc_bind2<FID>(a.winv, a.r, id, a.n, wi0, wi1);
+    sc_bind2<FID>(a.ts, a.r, id, a.n, ts0, ts1);
+    acc.add(a, sc_eq_factor<FID>(a.eqL, a.eqR, a.shift, a.mask, id), true, t0, t1, ti0, ti1, w0, w1, wi0, wi1, ts0);
   }
   acc.flush();
 }
@@ -214,7 +188,7 @@ template <int FID> NMX_DEV void sc_pps_inner_sums_lane(const ScPpsInnerArgs<FID>
       const size_t hi = (size_t)id + a.n;
       a0 = ld<FID>(a.a, id), a1 = ld<FID>(a.a, hi), b0 = ld<FID>(a.b, id), b1 = ld<FID>(a.b, hi), c0 = ld<FID>(a.c, id), c1 = ld<FID>(a.c, hi);
     }
-    acc.add(sc_pps_factor<FID>(a.eqL, a.eqR, a.shift, a.mask, id), wi, a0, a1, b0, b1, c0, c1, e0);
+    acc.add(sc_eq_factor<FID>(a.eqL, a.eqR, a.shift, a.mask, id), wi, a0, a1, b0, b1, c0, c1, e0);
   }
   acc.flush();
 }
@@ -223,11 +197,11 @@ template <int FID> NMX_DEV void sc_pps_inner_bind_lane(const ScPpsInnerArgs<FID>
   for (uint64_t i64 = first; i64 < a.n; i64 += stride) {
     const uint32_t id = (uint32_t)i64;
     F a0, a1, b0, b1, c0, c1, e0, e1;
-    sc_pps_bind2<FID>(a.a, a.r, id, a.n, a0, a1);
-    sc_pps_bind2<FID>(a.b, a.r, id, a.n, b0, b1);
-    sc_pps_bind2<FID>(a.c, a.r, id, a.n, c0, c1);
-    sc_pps_bind2<FID>(a.e, a.r, id, a.n, e0, e1);
-    acc.add(sc_pps_factor<FID>(a.eqL, a.eqR, a.shift, a.mask, id), true, a0, a1, b0, b1, c0, c1, e0);
+    sc_bind2<FID>(a.a, a.r, id, a.n, a0, a1);
+    sc_bind2<FID>(a.b, a.r, id, a.n, b0, b1);
+    sc_bind2<FID>(a.c, a.r, id, a.n, c0, c1);
+    sc_bind2<FID>(a.e, a.r, id, a.n, e0, e1);
+    acc.add(sc_eq_factor<FID>(a.eqL, a.eqR, a.shift, a.mask, id), true, a0, a1, b0, b1, c0, c1, e0);
   }
   acc.flush();
 }
@@ -267,78 +241,62 @@ template <int FID> NMX_DEV void sc_pps_wit_bind_lane(const ScPpsWitArgs<FID>& a,
   for (uint64_t i64 = first; i64 < a.n; i64 += stride) {
     const uint32_t id = (uint32_t)i64;
     F a0, a1, b0, b1;
-    sc_pps_bind2<FID>(a.w, a.r, id, a.n, a0, a1);
-    sc_pps_bind2<FID>(a.m, a.r, id, a.n, b0, b1);
+    sc_bind2<FID>(a.w, a.r, id, a.n, a0, a1);
+    sc_bind2<FID>(a.m, a.r, id, a.n, b0, b1);
     acc.add(a0, a1, b0, b1);
   }
   acc.flush();
 }
 
+// ---- the six sums-bearing lane bodies as passes of k_sc_sums ---------------------------------------------------------------------------
+template <int FID> struct ScPpsMemSums {
+  using Args = ScPpsMemArgs<FID>;
+  using Acc = ScPpsMemAcc<FID>;
+  static constexpr int J = 6;
+  static NMX_DEV void lane(const Args& a, uint32_t first, uint32_t stride, Acc& acc) { sc_pps_mem_sums_lane<FID>(a, first, stride, acc); }
+};
+template <int FID> struct ScPpsMemBindSums {
+  using Args = ScPpsMemArgs<FID>;
+  using Acc = ScPpsMemAcc<FID>;
+  static constexpr int J = 6;
+  static NMX_DEV void lane(const Args& a, uint32_t first, uint32_t stride, Acc& acc) { sc_pps_mem_bind_lane<FID>(a, first, stride, acc); }
+};
+template <int FID> struct ScPpsInnerSums {
+  using Args = ScPpsInnerArgs<FID>;
+  using Acc = ScPpsInnerAcc<FID>;
+  static constexpr int J = 4;
+  static NMX_DEV void lane(const Args& a, uint32_t first, uint32_t stride, Acc& acc) { sc_pps_inner_sums_lane<FID>(a, first, stride, acc); }
+};
+template <int FID> struct ScPpsInnerBindSums {
+  using Args = ScPpsInnerArgs<FID>;
+  using Acc = ScPpsInnerAcc<FID>;
+  static constexpr int J = 4;
+  static NMX_DEV void lane(const Args& a, uint32_t first, uint32_t stride, Acc& acc) { sc_pps_inner_bind_lane<FID>(a, first, stride, acc); }
+};
+template <int FID> struct ScPpsWitSums {
+  using Args = ScPpsWitArgs<FID>;
+  using Acc = ScPpsWitAcc<FID>;
+  static constexpr int J = 2;
+  static NMX_DEV void lane(const Args& a, uint32_t first, uint32_t stride, Acc& acc) { sc_pps_wit_sums_lane<FID>(a, first, stride, acc); }
+};
+template <int FID> struct ScPpsWitBindSums {
+  using Args = ScPpsWitArgs<FID>;
+  using Acc = ScPpsWitAcc<FID>;
+  static constexpr int J = 2;
+  static NMX_DEV void lane(const Args& a, uint32_t first, uint32_t stride, Acc& acc) { sc_pps_wit_bind_lane<FID>(a, first, stride, acc); }
+};
+
 // ---- the last device bind over [0, a.n = len / 2), all 16 tables: no sums; the bound (bind = 0: the unchanged) tables also land in the
 // staging area.  (The table loop is unrolled: a table chosen by a run-time index would cost a copy of the arguments in scratch.)
 template <int FID> NMX_DEV void sc_pps_bind_only_lane(const ScPpsBindArgs<FID>& a, uint32_t first, uint32_t stride) {
-  using F = Fp<FID>;
   for (uint64_t i64 = first; i64 < a.n; i64 += stride) {
     const uint32_t id = (uint32_t)i64;
 #pragma unroll
-    for (uint32_t t = 0; t < kScPpsTables; t++) {
-      uint32_t* X = a.X[t];
-      F y = ld<FID>(X, id);
-      if (a.bind) {
-        const F x1 = ld<FID>(X, (size_t)id + a.n);
-        y = (y + a.r * F::sub2(x1, y).norm()).norm().canon();
-        y.to_words(X + 8 * (size_t)id);
-      }
-      y.to_words(a.stage + 8 * ((size_t)t * a.n + id));
-    }
+    for (uint32_t t = 0; t < kScPpsTables; t++) sc_bind_stage_one<FID>(a.X[t], a.r, a.n, a.bind, a.stage, t, id);
   }
 }
 
 #if defined(__HIPCC__) || defined(__HIP__)
-// Launch bounds 256: DESIGN.md ("ppsnark sum-check") has the compiler's register, scratch and occupancy figures.
-template <int FID, int J, class ACC> __device__ __forceinline__ void sc_pps_block_out(ACC& acc, uint32_t* lds, uint32_t* partial) {
-  block_sum_waves<FID, J, true>(acc.s, lds);
-  if (threadIdx.x == 0) {
-#pragma unroll
-    for (int j = 0; j < J; j++) acc.s[j].to_words(partial + 8 * (J * (size_t)blockIdx.x + j));
-  }
-}
-template <int FID> __global__ __launch_bounds__(256) void k_pps_mem_sums(ScPpsMemArgs<FID> a, uint32_t* partial) {
-  __shared__ uint32_t lds[36 * 6];
-  ScPpsMemAcc<FID> acc;
-  sc_pps_mem_sums_lane<FID>(a, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, acc);
-  sc_pps_block_out<FID, 6>(acc, lds, partial);
-}
-template <int FID> __global__ __launch_bounds__(256) void k_pps_mem_bind_sums(ScPpsMemArgs<FID> a, uint32_t* partial) {
-  __shared__ uint32_t lds[36 * 6];
-  ScPpsMemAcc<FID> acc;
-  sc_pps_mem_bind_lane<FID>(a, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, acc);
-  sc_pps_block_out<FID, 6>(acc, lds, partial);
-}
-template <int FID> __global__ __launch_bounds__(256) void k_pps_inner_sums(ScPpsInnerArgs<FID> a, uint32_t* partial) {
-  __shared__ uint32_t lds[36 * 4];
-  ScPpsInnerAcc<FID> acc;
-  sc_pps_inner_sums_lane<FID>(a, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, acc);
-  sc_pps_block_out<FID, 4>(acc, lds, partial);
-}
-template <int FID> __global__ __launch_bounds__(256) void k_pps_inner_bind_sums(ScPpsInnerArgs<FID> a, uint32_t* partial) {
-  __shared__ uint32_t lds[36 * 4];
-  ScPpsInnerAcc<FID> acc;
-  sc_pps_inner_bind_lane<FID>(a, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, acc);
-  sc_pps_block_out<FID, 4>(acc, lds, partial);
-}
-template <int FID> __global__ __launch_bounds__(256) void k_pps_wit_sums(ScPpsWitArgs<FID> a, uint32_t* partial) {
-  __shared__ uint32_t lds[36 * 2];
-  ScPpsWitAcc<FID> acc;
-  sc_pps_wit_sums_lane<FID>(a, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, acc);
-  sc_pps_block_out<FID, 2>(acc, lds, partial);
-}
-template <int FID> __global__ __launch_bounds__(256) void k_pps_wit_bind_sums(ScPpsWitArgs<FID> a, uint32_t* partial) {
-  __shared__ uint32_t lds[36 * 2];
-  ScPpsWitAcc<FID> acc;
-  sc_pps_wit_bind_lane<FID>(a, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u, acc);
-  sc_pps_block_out<FID, 2>(acc, lds, partial);
-}
 template <int FID> __global__ __launch_bounds__(256) void k_pps_bind_only(ScPpsBindArgs<FID> a) {
   sc_pps_bind_only_lane<FID>(a, blockIdx.x * 256u + threadIdx.x, gridDim.x * 256u);
 }
@@ -347,36 +305,26 @@ template <int FID> __global__ __launch_bounds__(256) void k_pps_bind_only(ScPpsB
 static constexpr size_t kScPpsPartialBytes = (size_t)4096 * 6 * 32;
 static constexpr uint32_t kScPpsSlots = 4;  // mailbox slots 0..3: memory row, memory col, inner, witness
 
-// the device side of one proof: the launches over the 16 in-place tables, the context's stream
-template <int FID> struct ScPpsDev {
-  using F = Fp<FID>;
-  using H = HostFp4<FID>;
-  using Tables = typename ScEqDev<FID>::Tables;
+// the device side of one proof: the launches over the 16 in-place tables; the arena holds the four partials areas, then the staging
+// area of 16 x tail_len elements
+template <int FID> struct ScPpsDev : ScInplaceDev<FID> {
+  using Base = ScInplaceDev<FID>;
+  using typename Base::F;
+  using typename Base::H;
+  using typename Base::Tables;
+  using Base::h;
   using Sums = typename ScPps<FID>::Sums;
-  ScDev<FID>& h;
   uint32_t* X[kScPpsTables];
-  F nk, one;
-  uint32_t* stage;  // behind the four partials areas: 16 x tail_len elements
   uint32_t seq[kScPpsSlots] = {};
-  ScPpsDev(ScDev<FID>& h_, void* const* tables) : h(h_), stage((uint32_t*)(h_.c.arena + kScPpsSlots * kScPpsPartialBytes)) {
+  ScPpsDev(ScDev<FID>& h_, void* const* tables) : Base(h_, kScPpsSlots * kScPpsPartialBytes) {
     for (uint32_t t = 0; t < kScPpsTables; t++) X[t] = (uint32_t*)tables[t];
-    F fm = F::zero();  // the form factor as a plain integer, as ScPass<FID, 3>
-    if (h.mont) fm = pow2_plain<FID>(256);
-    else fm.l[0] = 1;
-    one = fm.canon();
-    nk = F::sub2(F::zero(), one).norm().canon();
   }
-  uint32_t* partial(uint32_t slot) const { return (uint32_t*)(h.c.arena + slot * kScPpsPartialBytes); }
-  static uint32_t blocks(uint32_t n) { return sc_blocks_bind(n); }  // one index per lane, at most 4096 blocks (the partials' areas)
-  template <int J> void finish(uint32_t slot, uint32_t nblocks) {
-    seq[slot] = h.next_seq();
-    hipLaunchKernelGGL((k_sum_partials_mail<FID, J, J>), dim3(1), dim3(256), 0, h.c.stream, partial(slot), nblocks, h.slot_dev(slot), seq[slot]);
-    HIPCHK(hipGetLastError());
-    h.launched(2);
+  template <class P> void pass(uint32_t slot, const typename P::Args& a) {
+    seq[slot] = this->template launch_pass<P>(slot, (uint32_t*)(h.c.arena + slot * kScPpsPartialBytes), a);
   }
   ScPpsMemArgs<FID> mem_args(uint32_t g, size_t off, const Tables& t, uint32_t n, const F& r, bool with_inf) const {
     uint32_t* const* T = X + 5 * g;
-    return ScPpsMemArgs<FID>{T[0] + 8 * off, T[1] + 8 * off, T[2] + 8 * off, T[3] + 8 * off, T[4] + 8 * off, r, nk, one,
+    return ScPpsMemArgs<FID>{T[0] + 8 * off, T[1] + 8 * off, T[2] + 8 * off, T[3] + 8 * off, T[4] + 8 * off, r, this->nk, this->one,
                              t.eqL, t.eqR, t.shift, t.mask, n, with_inf ? 1u : 0u};
   }
   ScPpsInnerArgs<FID> inner_args(size_t off, const Tables& t, uint32_t n, const F& r, bool with_inf) const {
@@ -384,40 +332,23 @@ template <int FID> struct ScPpsDev {
   }
   // the sums pass of memory group g over tables of len elements; high: the t(1) form over the high halves
   void mem_sums(uint32_t g, size_t len, const Tables& t, bool high) {
-    const uint32_t n = (uint32_t)(len / 2), nb = blocks(n);
-    hipLaunchKernelGGL((k_pps_mem_sums<FID>), dim3(nb), dim3(256), 0, h.c.stream, mem_args(g, high ? len / 2 : 0, t, n, F::zero(), !high), partial(g));
-    HIPCHK(hipGetLastError());
-    finish<6>(g, nb);
+    pass<ScPpsMemSums<FID>>(g, mem_args(g, high ? len / 2 : 0, t, (uint32_t)(len / 2), F::zero(), !high));
   }
   void inner_sums(size_t len, const Tables& t, bool high) {
-    const uint32_t n = (uint32_t)(len / 2), nb = blocks(n);
-    hipLaunchKernelGGL((k_pps_inner_sums<FID>), dim3(nb), dim3(256), 0, h.c.stream, inner_args(high ? len / 2 : 0, t, n, F::zero(), !high), partial(2));
-    HIPCHK(hipGetLastError());
-    finish<4>(2, nb);
+    pass<ScPpsInnerSums<FID>>(2, inner_args(high ? len / 2 : 0, t, (uint32_t)(len / 2), F::zero(), !high));
   }
   // round 1: the 18 sums over the tables as they are (tR: eq(rhos)'s tables of the round, tO: eq(r_outer)'s)
   void sums(size_t len, const Tables& tR, const Tables& tO) {
     mem_sums(0, len, tR, false), mem_sums(1, len, tR, false), inner_sums(len, tO, false);
-    const uint32_t n = (uint32_t)(len / 2), nb = blocks(n);
-    hipLaunchKernelGGL((k_pps_wit_sums<FID>), dim3(nb), dim3(256), 0, h.c.stream, ScPpsWitArgs<FID>{X[14], X[15], F::zero(), n}, partial(3));
-    HIPCHK(hipGetLastError());
-    finish<2>(3, nb);
+    pass<ScPpsWitSums<FID>>(3, ScPpsWitArgs<FID>{X[14], X[15], F::zero(), (uint32_t)(len / 2)});
   }
   // bind the 16 tables (len elements, len >= 4) with r in place and take the next round's sums (its eq tables: tR, tO)
   void bind_sums(size_t len, const H& r, const Tables& tR, const Tables& tO) {
     const F rd = r.to_device();
-    const uint32_t n = (uint32_t)(len / 4), nb = blocks(n);
-    for (uint32_t g = 0; g < 2; g++) {
-      hipLaunchKernelGGL((k_pps_mem_bind_sums<FID>), dim3(nb), dim3(256), 0, h.c.stream, mem_args(g, 0, tR, n, rd, true), partial(g));
-      HIPCHK(hipGetLastError());
-      finish<6>(g, nb);
-    }
-    hipLaunchKernelGGL((k_pps_inner_bind_sums<FID>), dim3(nb), dim3(256), 0, h.c.stream, inner_args(0, tO, n, rd, true), partial(2));
-    HIPCHK(hipGetLastError());
-    finish<4>(2, nb);
-    hipLaunchKernelGGL((k_pps_wit_bind_sums<FID>), dim3(nb), dim3(256), 0, h.c.stream, ScPpsWitArgs<FID>{X[14], X[15], rd, n}, partial(3));
-    HIPCHK(hipGetLastError());
-    finish<2>(3, nb);
+    const uint32_t n = (uint32_t)(len / 4);
+    for (uint32_t g = 0; g < 2; g++) pass<ScPpsMemBindSums<FID>>(g, mem_args(g, 0, tR, n, rd, true));
+    pass<ScPpsInnerBindSums<FID>>(2, inner_args(0, tO, n, rd, true));
+    pass<ScPpsWitBindSums<FID>>(3, ScPpsWitArgs<FID>{X[14], X[15], rd, n});
   }
   // the pending sums of the four groups as elements
   Sums collect(const Tables& tR, const Tables& tO) {
@@ -456,99 +387,73 @@ template <int FID> struct ScPpsDev {
     }
     return t1_val[d];
   }
-  // the hand-over: bind with r (rp == nullptr: no bind) and bring the 16 tables of `half` elements to the host
   void to_host(size_t half, const H* rp, std::vector<H>* T) {
-    require(half >= 1 && half <= kTailMax, NMX_E_HIP, "sum-check: tail hand-over out of range");
-    ScPpsBindArgs<FID> a;
-    for (uint32_t t = 0; t < kScPpsTables; t++) a.X[t] = X[t];
-    a.r = rp ? rp->to_device() : F::zero();
-    a.stage = stage, a.n = (uint32_t)half, a.bind = rp ? 1u : 0u;
-    hipLaunchKernelGGL((k_pps_bind_only<FID>), dim3(blocks(a.n)), dim3(256), 0, h.c.stream, a);
-    HIPCHK(hipGetLastError());
-    h.launched();
-    std::vector<uint32_t> land((size_t)kScPpsTables * half * 8);
-    HIPCHK(hipMemcpyAsync(land.data(), stage, land.size() * 4, hipMemcpyDeviceToHost, h.c.stream));
-    stream_wait(h.c.stream);
-    for (uint32_t t = 0; t < kScPpsTables; t++) {
-      T[t].resize(half);
-      const uint32_t* src = land.data() + 8 * ((size_t)t * half);
-      for (size_t x = 0; x < half; x++) T[t][x] = h.stored(src + 8 * x);
-    }
+    Base::to_host(
+        half, rp, kScPpsTables,
+        [&](const F& r, uint32_t n, uint32_t bind) {
+          ScPpsBindArgs<FID> a;
+          for (uint32_t t = 0; t < kScPpsTables; t++) a.X[t] = X[t];
+          a.r = r, a.stage = this->stage, a.n = n, a.bind = bind;
+          hipLaunchKernelGGL((k_pps_bind_only<FID>), dim3(Base::blocks(n)), dim3(256), 0, h.c.stream, a);
+        },
+        [&](uint32_t t) -> std::vector<H>& { return T[t]; });
   }
 };
 
-// RelaxedR1CSSNARK::prove_helper (ppsnark.rs:886-983).  Of the sc_* options only sc_host_tail and sc_poll_us apply.
-template <int FID>
-static void sc_prove_ppsnark_t(Ctx& c, size_t num_rounds, void* const* tables, const void* rhos, const void* r_outer, const void* claims2,
-                               const void* coeffs9, uint32_t flags, TranscriptFn cb, void* cb_ctx, uint8_t* out_polys, uint8_t* out_r,
-                               uint8_t* out_finals) {
+// RelaxedR1CSSNARK::prove_helper (ppsnark.rs:886-983) as a prover of sc_prove_inplace
+template <int FID> struct ScPpsProver {
   using H = HostFp4<FID>;
-  const auto T0 = std::chrono::steady_clock::now();
-  const uint32_t l = (uint32_t)num_rounds;
-  try {
-    ScDev<FID> h(c, flags);
-    try {
-      // every scalar is read (and range-checked) before anything is launched (the C entry point has checked them already, before it
-      // leased a device; this layer does not rely on that)
-      ScPps<FID> st;
-      st.init(h.alg, rhos, r_outer, claims2, coeffs9, l);
-      size_t len = (size_t)1 << l;
-      arena_reserve(c, kScPpsSlots * kScPpsPartialBytes + pad256((size_t)kScPpsTables * kTailMax * 32) + 512);
-      ScEqDev<FID> eqR, eqO;
-      if (len > h.tail_len) {
-        const size_t hb = pad256(ScEqDev<FID>::heap_bytes(l));
-        aux_reserve(c, 2 * hb);
-        eqR.init(h, st.eq[0], c.aux);
-        eqO.init(h, st.eq[4], c.aux + hb);
-      }
-      ScPpsDev<FID> dev(h, tables);
-      std::vector<H> hT[kScPpsTables];
-      uint32_t j = 1;
-      if (len <= h.tail_len) {
-        dev.to_host(len, nullptr, hT);  // the whole instance fits the tail
-      } else {
-        typename ScEqDev<FID>::Tables tR = eqR.tables(1), tO = eqO.tables(1);
-        dev.sums(len, tR, tO);
-        for (;; j++) {
-          const typename ScPps<FID>::Sums s = dev.collect(tR, tO);
-          dev.new_round();
-          H co[4];
-          st.round_poly(s, [&](uint32_t d) { return dev.t1(d, len, tR, tO); }, co);
-          const H r = h.ask(cb, cb_ctx, co, 4, out_polys ? out_polys + 128 * (size_t)(j - 1) : nullptr, out_r ? out_r + 32 * (size_t)(j - 1) : nullptr);
-          st.bound(co, r);
-          h.prof.rounds++;
-          if (len / 2 <= h.tail_len) {  // the last device bind: no sums, the bound tables go to the host
-            dev.to_host(len / 2, &r, hT);
-            len /= 2;
-            j++;
-            break;
-          }
-          tR = eqR.tables(j + 1), tO = eqO.tables(j + 1);
-          dev.bind_sums(len, r, tR, tO);
-          len /= 2;
-        }
-      }
-      if (j <= l) {
-        h.prof.host_rounds += l - j + 1;
-        sc_tail_rounds_ppsnark<FID>(h.alg, st, l, j, hT, cb, cb_ctx, out_polys, out_r);
-      }
-      if (out_finals)
-        for (uint32_t t = 0; t < kScPpsTables; t++) h.alg.out(hT[t][0], out_finals + 32 * t);
-      stream_wait(c.stream);  // the (partly bound) tables are the caller's again
-      h.finish_profile(std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - T0).count());
-    } catch (...) {
-      h.sync_all_quiet();  // whatever failed: no kernel of this call still writes the tables
-      throw;
+  void* const* tables;
+  const void *rhos, *r_outer, *claims2, *coeffs9;
+  TranscriptFn cb;
+  void* cb_ctx;
+  uint8_t *out_polys, *out_r, *out_finals;
+  ScPps<FID> st;
+  ScEqDev<FID> eqR, eqO;
+  std::optional<ScPpsDev<FID>> dev;
+  std::vector<H> hT[kScPpsTables];
+  typename ScEqDev<FID>::Tables tR, tO;  // of the round the pending sums belong to
+
+  void read_scalars(const ScAlg<FID>& alg, uint32_t l) { st.init(alg, rhos, r_outer, claims2, coeffs9, l); }
+  void reserve(ScDev<FID>& h, uint32_t l, bool device_rounds) {
+    arena_reserve(h.c, kScPpsSlots * kScPpsPartialBytes + pad256((size_t)kScPpsTables * kTailMax * 32) + 512);
+    if (device_rounds) {
+      const size_t hb = pad256(ScEqDev<FID>::heap_bytes(l));
+      aux_reserve(h.c, 2 * hb);
+      eqR.init(h, st.eq[0], h.c.aux);
+      eqO.init(h, st.eq[4], h.c.aux + hb);
     }
-  } catch (const ScFail& f) {
-    rethrow(f);
+    dev.emplace(h, tables);
   }
-}
+  void first_sums(size_t len) {
+    tR = eqR.tables(1), tO = eqO.tables(1);
+    dev->sums(len, tR, tO);
+  }
+  void round_poly(size_t len, H* co) {
+    const typename ScPps<FID>::Sums s = dev->collect(tR, tO);
+    dev->new_round();
+    st.round_poly(s, [&](uint32_t d) { return dev->t1(d, len, tR, tO); }, co);
+  }
+  void bound(const H* co, const H& r) { st.bound(co, r); }
+  void bind_sums(size_t len, const H& r, uint32_t next) {
+    tR = eqR.tables(next), tO = eqO.tables(next);
+    dev->bind_sums(len, r, tR, tO);
+  }
+  void to_host(size_t half, const H* rp) { dev->to_host(half, rp, hT); }
+  void host_tail(const ScAlg<FID>& alg, uint32_t l, uint32_t j) { sc_tail_rounds_ppsnark<FID>(alg, st, l, j, hT, cb, cb_ctx, out_polys, out_r); }
+  void outputs(const ScAlg<FID>& alg) {
+    if (out_finals)
+      for (uint32_t t = 0; t < kScPpsTables; t++) alg.out(hT[t][0], out_finals + 32 * t);
+  }
+};
 
 void fv_sumcheck_prove_ppsnark(Ctx& c, int field, size_t num_rounds, void* const* tables, const void* rhos, const void* r_outer,
                                const void* claims2, const void* coeffs9, uint32_t flags, TranscriptFn cb, void* cb_ctx, uint8_t* out_polys,
                                uint8_t* out_r, uint8_t* out_finals) {
-  with_field(field, [&](auto F) { sc_prove_ppsnark_t<F()>(c, num_rounds, tables, rhos, r_outer, claims2, coeffs9, flags, cb, cb_ctx, out_polys, out_r, out_finals); });
+  with_field(field, [&](auto F) {
+    ScPpsProver<F()> p{tables, rhos, r_outer, claims2, coeffs9, cb, cb_ctx, out_polys, out_r, out_finals};
+    sc_prove_inplace<F()>(c, flags, num_rounds, p);
+  });
 }
 #endif
 

@@ -1065,10 +1065,7 @@ template <int FID, int MODE> struct ScPass {
   ScPass(ScDev<FID>& h_, void* a, void* b, void* cc, uint32_t* partial_, uint32_t slot_)
       : h(h_), A((uint32_t*)a), B((uint32_t*)b), C((uint32_t*)cc), partial(partial_), slot(slot_), stream(h_.c.stream) {
     F fconst = F::zero();
-    if (MODE == 3) {
-      if (h.mont) fconst = pow2_plain<FID>(256);
-      else fconst.l[0] = 1;
-    }
+    if (MODE == 3) fconst = sc_form_factor<FID>(h.mont);
     nk = MODE == 3 ? F::sub2(F::zero(), fconst.canon()).norm().canon() : F::zero();  // p - k, as eq_sums_t
   }
   static constexpr uint32_t kFactors = MODE == 3 ? 3u : 2u;  // stored factors per term without eqL

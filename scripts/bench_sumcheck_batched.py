@@ -7,7 +7,7 @@
 
 Both paths see the same transcript (SHA3 stand-in, tests/spartan_common.StandInTranscript) and must return the same round polynomials;
 that is asserted once per shape before anything is timed.  Times are a host clock around synchronous calls and include the device-side
-copy of the tables, which both paths pay.  Prints a table and one JSON line.  Its default shapes have not been run on a GPU yet: docs/measurements.md.
+copy of the tables, which both paths pay.  Prints a table and one JSON line.  docs/measurements.md has the one run of its default shapes.
 
   python scripts/bench_sumcheck_batched.py                       # BN254 Fr, 2^14 and 2^20, k = 1, 3, 8, 10 repetitions
   python scripts/bench_sumcheck_batched.py --sizes 12 --ks 2 --reps 3
@@ -55,7 +55,9 @@ def run_shape(lg, k, reps, warm):
     i32 = lambda b: int.from_bytes(b, "little")  # noqa: E731
 
     def fresh():
-        return [[t.clone() for t in row] for row in src]
+        out = [[t.clone() for t in row] for row in src]
+        torch.cuda.synchronize()  # the copies run on torch's stream; the library's stream is not ordered behind it
+        return out
 
     def new_path():
         A, B, C = fresh()

@@ -64,6 +64,7 @@ def run_shape(lg, reps, warm):
 
     def new_path():
         T = [t.clone() for t in src]
+        torch.cuda.synchronize()  # the copies run on torch's stream; the library's stream is not ordered behind it
         tr = sp.StandInTranscript(p)
         polys, _r, _fin = fv.sumcheck_prove_ppsnark(FID, T, rho_v, ro_v, [sp.le(c) for c in claims2], [sp.le(c) for c in coeffs], tr)
         return polys
@@ -77,6 +78,7 @@ def run_shape(lg, reps, warm):
 
     def composed_path():
         T = [t.clone() for t in src]
+        torch.cuda.synchronize()  # the copies run on torch's stream; the library's stream is not ordered behind it
         tr = sp.StandInTranscript(p)
         running = [0] * 6 + [None, claims2[1], None]
         e = (coeffs[6] * claims2[0] + coeffs[7] * claims2[1]) % p

@@ -1,8 +1,8 @@
-// tests/host_emul/sc_batched_emul.cpp -- TEST-ONLY: the lane bodies of the batched cubic sum-check's kernels (k_scb_sums,
-// k_scb_bind_sums, k_scb_bind_only: nova_amd/csrc/sumcheck_batched.hpp) on the CPU, one fiber per thread (simt.hpp), limb bounds asserted
+// tests/host_emul/sc_batched_emul.cpp -- TEST-ONLY: the lane bodies of the batched cubic sum-check's kernels (k_sc_sums over ScBatchedSums
+// and ScBatchedBindSums, k_scb_bind_only: nova_amd/csrc/sumcheck_batched.hpp, sumcheck_inplace.hpp) on the CPU, one fiber per thread (simt.hpp), limb bounds asserted
 // (NMX_DEBUG_BOUNDS).  Tables, eq tables, the alphas and the challenge in the device's internal form come from the test
 // (tests/test_sumcheck_batched_abi.py), so the host half of the call is not trusted here.  Every lane's pair of canonical sums is
-// handed back; the test adds them up.  NOT emulated: the block reduction (block_sum_pair: shuffles), k_sum_partials_mail and the host
+// handed back; the test adds them up.  NOT emulated: the block reduction (block_sum_waves: shuffles), k_sum_partials_mail and the host
 // half (eq heaps, mailbox, round algebra) -- those run in tests/test_gpu_sumcheck_batched.py only.
 #include <stdint.h>
 #include <string.h>

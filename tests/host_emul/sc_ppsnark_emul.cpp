@@ -1,5 +1,5 @@
-// tests/host_emul/sc_ppsnark_emul.cpp -- TEST-ONLY: the lane bodies of the ppsnark sum-check's kernels (k_pps_mem_sums / _bind_sums,
-// k_pps_inner_sums / _bind_sums, k_pps_wit_sums / _bind_sums, k_pps_bind_only: nova_amd/csrc/sumcheck_ppsnark.hpp) on the CPU, one fiber
+// tests/host_emul/sc_ppsnark_emul.cpp -- TEST-ONLY: the lane bodies of the ppsnark sum-check's kernels (k_sc_sums over ScPpsMemSums / ..BindSums,
+// ScPpsInnerSums / ..BindSums, ScPpsWitSums / ..BindSums; k_pps_bind_only: nova_amd/csrc/sumcheck_ppsnark.hpp, sumcheck_inplace.hpp) on the CPU, one fiber
 // per thread (simt.hpp), limb bounds asserted (NMX_DEBUG_BOUNDS).  Tables, eq tables, the constants and the challenge in the device's
 // internal form come from the test (tests/test_sumcheck_ppsnark_abi.py), so the host half of the call is not trusted here.  Every lane's
 // canonical sums are handed back; the test adds them up.  NOT emulated: the block reductions (block_sum_waves: shuffles), the mailbox sum

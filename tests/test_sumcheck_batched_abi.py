@@ -221,7 +221,7 @@ BIG = 3 * 256 + 1      # three blocks' worth of indices and one more: a partial 
 
 @pytest.fixture(scope="module")
 def E():
-    deps = [EMUL_SRC, os.path.join(ROOT, "tests", "host_emul", "simt.hpp")] + [os.path.join(CSRC, f) for f in ("fp.hpp", "sumcheck_batched.hpp", "spmv_row.hpp",
+    deps = [EMUL_SRC, os.path.join(ROOT, "tests", "host_emul", "simt.hpp")] + [os.path.join(CSRC, f) for f in ("fp.hpp", "sumcheck_batched.hpp", "sumcheck_inplace.hpp", "spmv_row.hpp",
                                                                                                             "msm_partition.hpp")]
     if not os.path.exists(EMUL_SO) or os.path.getmtime(EMUL_SO) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-DNMX_DEBUG_BOUNDS", "-shared", "-fPIC", "-o", EMUL_SO, EMUL_SRC])

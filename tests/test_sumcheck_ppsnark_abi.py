@@ -237,7 +237,7 @@ NTAB, NSUM = {MEM: 5, INNER: 4, WIT: 2, ALL: 16}, {MEM: 6, INNER: 4, WIT: 2}
 
 @pytest.fixture(scope="module")
 def E():
-    deps = [EMUL_SRC, os.path.join(ROOT, "tests", "host_emul", "simt.hpp")] + [os.path.join(CSRC, f) for f in ("fp.hpp", "sumcheck_ppsnark.hpp", "spmv_row.hpp",
+    deps = [EMUL_SRC, os.path.join(ROOT, "tests", "host_emul", "simt.hpp")] + [os.path.join(CSRC, f) for f in ("fp.hpp", "sumcheck_ppsnark.hpp", "sumcheck_inplace.hpp", "spmv_row.hpp",
                                                                                                             "msm_partition.hpp")]
     if not os.path.exists(EMUL_SO) or os.path.getmtime(EMUL_SO) < max(os.path.getmtime(d) for d in deps):
         subprocess.check_call(["g++", "-O2", "-std=c++17", "-DNMX_DEBUG_BOUNDS", "-shared", "-fPIC", "-o", EMUL_SO, EMUL_SRC])
