@@ -591,6 +591,45 @@ int nmx_ppsnark_mem_oracles(int field_id, size_t k, size_t n,
                             const void* gamma, const void* r, uint32_t flags,
                             void* const* out_t_plus_r, void* const* out_w_plus_r,
                             void* const* out_t_plus_r_inv, void* const* out_w_plus_r_inv);
+/* ---- ppsnark's key tables: the Spark representation, its timestamps and the masked eq table, produced in HBM ---------------------------
+ * nmx_ppsnark_spark_repr == R1CSShapeSparkRepr::new (src/spartan/ppsnark.rs:117-190) over matrices that are already resident: no N-sized
+ * vector is built on the host.  handles are k matrices from nmx_spmv_register, 1 <= k <= 8, all over one field; the reference has k = 3:
+ * A, B, C.  With nnz_j the entry count of matrix j, off_j = nnz_0 + .. + nnz_(j-1) and total = off_k, entry e of matrix j is storage index
+ * e of its CSR arrays (the order of SparseMatrix::iter, src/r1cs/sparse.rs:332-390, chained in the order of the handles), and its row is
+ * the r with indptr[r] <= e < indptr[r + 1].  Every output is n field elements; for i < n:
+ *     out_row[i]      the row of entry i - off_j of the matrix j that i falls into; 0 for i >= total          (ppsnark.rs:123-128)
+ *     out_col[i]      that entry's column; n - 1 for i >= total (the lookup into the last, zero, entry of z)
+ *     out_vals[j][i]  the entry's value if off_j <= i < off_(j+1), else 0                                     (ppsnark.rs:129-151)
+ *     out_ts_row[a]   the number of i < n with row[i] == a; out_ts_col[a]: the same for col (timestamp_calc, ppsnark.rs:154-167).  The
+ *                     n - total padding elements count at address 0 for rows and n - 1 for columns; each vector sums to n.
+ * Integers become field elements as Scalar::from(u64) (ppsnark.rs:170-174): canonical words, or with NMX_SCALARS_MONT the value * 2^256
+ * mod p.  Values come out canonical (< p) in the same form, whatever form the matrix was registered in.  In the order of
+ * nmx_sumcheck_prove_ppsnark's tables: out_ts_row is NMX_PPS_TS_ROW and out_ts_col is NMX_PPS_TS_COL (and the ts inputs of
+ * nmx_ppsnark_mem_oracles); out_row / out_col are the addr inputs of nmx_field_gather (NMX_PPS_L_ROW, NMX_PPS_L_COL) and of
+ * nmx_ppsnark_mem_oracles; NMX_PPS_VAL is val_A + c val_B + c^2 val_C over out_vals (nmx_field_axpy2).
+ *   n          the caller's N: the library checks it and does not choose it (the reference's formula, ppsnark.rs:118-121, is
+ *              ppsnark_spark_size in the Python and C++ wrappers; R1CSShape::pad stays the caller's).  n must be a power of two, n >= total,
+ *              and n >= rows_j, n >= cols_j for every j -- every address is then below n, which nmx_field_gather and the memory check need.
+ *   flags      NMX_SCALARS_MONT; NMX_SCALARS_DEVICE: the outputs are HBM pointers on logical device 0, where matrices live, otherwise host
+ *              arrays filled through staging.  Any other flag is NMX_E_ARG -- NMX_ASYNC too: the call is synchronous.
+ *   outputs    any output pointer, any entry of out_vals and out_vals itself may be NULL: a NULL output is not computed.
+ * Errors found before a device is leased, with nothing written: NULL handles, k outside 1 .. 8, an unknown flag, n == 0 or no power of
+ * two, n below total or below some matrix's rows or columns (the message names the bound), matrices over different fields, two outputs
+ * that overlap: NMX_E_ARG; n >= 2^32: NMX_E_TOO_LARGE; an unknown handle: NMX_E_HANDLE.  The matrices are never modified.  Thread-safe,
+ * and ordered behind the calling thread's NMX_ASYNC calls like every synchronous call.  One expansion pass, ts_row from differences of
+ * indptr, ts_col as a block-aggregated integer histogram (nova_amd/csrc/ppsnark_key.hpp). */
+int nmx_ppsnark_spark_repr(const uint64_t* handles, size_t k, size_t n, uint32_t flags,
+                           void* out_row, void* out_col, void* const* out_vals /* k */,
+                           void* out_ts_row, void* out_ts_col);
+/* nmx_masked_eq_evals == MaskedEqPolynomial::evals (src/spartan/polys/masked_eq.rs:57-75, used at src/spartan/ppsnark.rs:284-285):
+ * out[2^ell] is what nmx_eq_evals_from_points(field_id, r, ell, flags, out) gives, with the first 2^num_masked_vars entries zero -- table
+ * NMX_PPS_MASKED_EQ of nmx_sumcheck_prove_ppsnark (r = r_outer_full, num_masked_vars = log2 num_vars).  r: ell x 32 bytes, host; out:
+ * host, or HBM with NMX_SCALARS_DEVICE; NMX_SCALARS_MONT as there; any other flag: NMX_E_ARG.  ell >= 31 or num_masked_vars > ell:
+ * NMX_E_ARG (num_masked_vars == ell gives an all-zero table: evals does not assert `<`, WitnessBoundSumcheck::new does); a coordinate
+ * r[i] >= p: NMX_E_SCALAR_RANGE; a NULL r with ell > 0, a NULL out or a field_id that is none of NMX_F_*: NMX_E_ARG.  All found before a
+ * device is leased; nothing written.  (field_id is not spelled `field`, as for nmx_field_gather: the closed list of
+ * tests/test_gpu_bad_field.py; the refusal of a bad id is checked in tests/test_ppsnark_key_abi.py and tests/test_gpu_ppsnark_key.py.) */
+int nmx_masked_eq_evals(int field_id, const void* r, size_t ell, size_t num_masked_vars, uint32_t flags, void* out);
 /* ---- inner-product argument (the evaluation engine of the secondary curve) -----------------------------------------------------
  * InnerProductArgument::prove (src/provider/ipa_pc.rs:174-281), reached through EvaluationEngine::prove (:69-82) -- the evaluation
  * argument of S2 in CompressedSNARK::prove (src/nova/mod.rs:862-881; Grumpkin / Pallas / Vesta engines, src/provider/mod.rs:38-148).

@@ -625,6 +625,27 @@ inline void ppsnark_mem_oracles(int field, size_t n, const std::vector<const voi
   check(nmx_ppsnark_mem_oracles(field, k, n, mem.data(), addr.data(), L.data(), ts.data(), gamma.data(), r.data(),
                                 kDev | (mont ? NMX_SCALARS_MONT : 0u), t_plus_r.data(), w_plus_r.data(), t_plus_r_inv.data(), w_plus_r_inv.data()));
 }
+// N of R1CSShapeSparkRepr::new (ppsnark.rs:118-121): max(total entries, 2 num_vars, num_cons).next_power_of_two()
+inline size_t ppsnark_spark_size(const std::vector<size_t>& nnzs, size_t num_vars, size_t num_cons) {
+  size_t m = 2 * num_vars > num_cons ? 2 * num_vars : num_cons, total = 0;
+  for (size_t z : nnzs) total += z;
+  if (total > m) m = total;
+  size_t n = 1;
+  while (n < m) n <<= 1;
+  return n;
+}
+// R1CSShapeSparkRepr::new (ppsnark.rs:117-190) over registered matrices (the reference: A, B, C): row, col, vals[j], ts_row, ts_col are HBM
+// vectors of n elements each; any may be nullptr (not computed), vals may be empty or hold one pointer per matrix
+inline void ppsnark_spark_repr(const std::vector<uint64_t>& mats, size_t n, void* row, void* col, const std::vector<void*>& vals, void* ts_row,
+                               void* ts_col, bool mont = false) {
+  if (!vals.empty() && vals.size() != mats.size()) throw std::invalid_argument("ppsnark_spark_repr: one value vector per matrix, or none");
+  check(nmx_ppsnark_spark_repr(mats.data(), mats.size(), n, kDev | (mont ? NMX_SCALARS_MONT : 0u), row, col, vals.empty() ? nullptr : vals.data(),
+                               ts_row, ts_col));
+}
+// MaskedEqPolynomial::evals (masked_eq.rs:57-75): eq_evals with the first 2^num_masked_vars entries zero; out: 2^r.size() elements in HBM
+inline void masked_eq_evals(int field, const std::vector<Scalar>& r, size_t num_masked_vars, void* out, bool mont = false) {
+  check(nmx_masked_eq_evals(field, r.data(), r.size(), num_masked_vars, kDev | (mont ? NMX_SCALARS_MONT : 0u), out));
+}
 // the sum-check provers over HBM-resident tables (bound in place); `cb` / `ctx`: nmx_transcript_fn and its state
 struct Proof {
   std::vector<uint8_t> polys, r, claims;

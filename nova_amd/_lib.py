@@ -135,6 +135,8 @@ def lib():
     L.nmx_sumcheck_prove_ppsnark.argtypes = [i, sz, vp, vp, vp, vp, vp, u32, TRANSCRIPT_FN, vp, vp, vp, vp]
     L.nmx_field_gather.argtypes = [i, vp, sz, vp, sz, u32, vp]
     L.nmx_ppsnark_mem_oracles.argtypes = [i, sz, sz, vp, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
+    L.nmx_ppsnark_spark_repr.argtypes = [vp, sz, sz, u32, vp, vp, vp, vp, vp]
+    L.nmx_masked_eq_evals.argtypes = [i, vp, sz, sz, u32, vp]
     L.nmx_ipa_prove.argtypes = [u64, vp, vp, vp, sz, u32, IPA_TRANSCRIPT_FN, vp, vp, vp, vp, vp]
     L.nmx_ipa_verify.argtypes = [u64, vp, vp, i, vp, vp, sz, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.nmx_set_profiling.argtypes = [i]

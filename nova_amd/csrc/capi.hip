@@ -2987,6 +2987,72 @@ int nmx_ppsnark_mem_oracles(int field_id, size_t k, size_t n, const void* const*
   });
 }
 
+// ---- ppsnark's key tables (ppsnark_key.hpp; src/spartan/ppsnark.rs:117-190 and src/spartan/polys/masked_eq.rs:57-75) ---------------------------
+// As above: every refusal comes before a device is leased, launches nothing and writes nothing.
+int nmx_ppsnark_spark_repr(const uint64_t* handles, size_t k, size_t n, uint32_t flags, void* out_row, void* out_col, void* const* out_vals,
+                           void* out_ts_row, void* out_ts_col) {
+  return guarded([&] {
+    require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE)) == 0, NMX_E_ARG,
+            "nmx_ppsnark_spark_repr: only NMX_SCALARS_MONT and NMX_SCALARS_DEVICE apply (the call is synchronous)");
+    require(handles != nullptr, NMX_E_ARG, "null argument");
+    require(k >= 1 && k <= 8, NMX_E_ARG, "nmx_ppsnark_spark_repr: k must be 1 .. 8");
+    require(n < (1ull << 32), NMX_E_TOO_LARGE, "nmx_ppsnark_spark_repr: n must stay below 2^32");
+    require(n >= 1 && (n & (n - 1)) == 0, NMX_E_ARG, "nmx_ppsnark_spark_repr: n must be a power of two");
+    std::vector<std::pair<uintptr_t, uintptr_t>> outs;
+    auto add = [&](void* p) {
+      if (p) outs.emplace_back((uintptr_t)p, (uintptr_t)p + n * 32);
+    };
+    add(out_row), add(out_col), add(out_ts_row), add(out_ts_col);
+    for (size_t j = 0; j < k && out_vals; j++) add(out_vals[j]);
+    std::sort(outs.begin(), outs.end());
+    for (size_t i = 1; i < outs.size(); i++) require(outs[i - 1].second <= outs[i].first, NMX_E_ARG, "nmx_ppsnark_spark_repr: two outputs overlap");
+    const auto sp = sparse_refs(handles, k);
+    std::vector<CsrView> mats(k);
+    std::vector<size_t> nnz(k);
+    size_t total = 0;
+    for (size_t j = 0; j < k; j++) {
+      const Global::SparseSet& ss = *sp[j];
+      if (ss.rows > n)
+        throw Fail{NMX_E_ARG, "nmx_ppsnark_spark_repr: matrix " + std::to_string(j) + " has " + std::to_string(ss.rows) + " rows > n = " + std::to_string(n)};
+      if (ss.cols > n)
+        throw Fail{NMX_E_ARG, "nmx_ppsnark_spark_repr: matrix " + std::to_string(j) + " has " + std::to_string(ss.cols) + " columns > n = " + std::to_string(n)};
+      mats[j] = ss.view(), nnz[j] = ss.nnz;
+      total += ss.nnz;
+    }
+    if (total > n)
+      throw Fail{NMX_E_ARG, "nmx_ppsnark_spark_repr: the matrices hold " + std::to_string(total) + " entries > n = " + std::to_string(n)};
+    if (outs.empty()) return;
+    CtxLease L;  // logical device 0, where matrices live; behind the calling thread's NMX_ASYNC calls
+    fv_ppsnark_spark_repr(*L.c, sp[0]->field, mats.data(), nnz.data(), k, n, flags, out_row, out_col, out_vals, out_ts_row, out_ts_col);
+  });
+}
+int nmx_masked_eq_evals(int field_id, const void* r, size_t ell, size_t num_masked_vars, uint32_t flags, void* out) {
+  return guarded([&] {
+    require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE)) == 0, NMX_E_ARG,
+            "nmx_masked_eq_evals: only NMX_SCALARS_MONT and NMX_SCALARS_DEVICE apply (the call is synchronous)");
+    require((r || ell == 0) && out, NMX_E_ARG, "null argument");
+    require(ell < 31, NMX_E_ARG, "too many variables");
+    require(num_masked_vars <= ell, NMX_E_ARG, "nmx_masked_eq_evals: num_masked_vars > ell");
+    with_field(field_id, [&](auto F) {
+      for (size_t i = 0; i < ell; i++) {
+        uint32_t w[8];
+        memcpy(w, (const uint8_t*)r + 32 * i, 32);
+        require(Fp<decltype(F)::value>::words_lt_p(w), NMX_E_SCALAR_RANGE, "challenge >= field modulus");
+      }
+    });
+    CtxLease L;
+    const size_t n = (size_t)1 << ell, masked = (size_t)1 << num_masked_vars;
+    const bool dev = flags & NMX_SCALARS_DEVICE;
+    if (!dev) aux_reserve(*L.c, n * 32);
+    void* dst = dev ? out : (void*)L.c->aux;
+    fv_eq_evals(*L.c, field_id, r, (uint32_t)ell, flags, (uint32_t*)dst);
+    // the first 2^m evaluations are zero (masked_eq.rs:68-72); zero is all-zero words in both layouts; behind the eq pass on the stream
+    HIPCHK(hipMemsetAsync(dst, 0, masked * 32, L.c->stream));
+    if (!dev) HIPCHK(hipMemcpyAsync(out, dst, n * 32, hipMemcpyDeviceToHost, L.c->stream));
+    HIPCHK(hipStreamSynchronize(L.c->stream));
+  });
+}
+
 // Device state of one call that has to outlive the MSMs the call runs (they re-carve the context's arena): the context's aux buffer
 // up to kAuxMax bytes, an allocation of the call's own above that; carved front to back.  `ev`, if the call creates it, goes with it.
 struct CallScratch {

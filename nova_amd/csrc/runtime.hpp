@@ -801,6 +801,11 @@ bool fv_gather(Ctx&, int field, const void* mem, size_t n_mem, const void* addr,
 bool fv_ppsnark_mem_oracles(Ctx&, int field, size_t k, size_t n, const void* const* mem, const void* const* addr, const void* const* L,
                             const void* const* ts, const void* gamma, const void* r, uint32_t flags, void* const* out_t_plus_r,
                             void* const* out_w_plus_r, void* const* out_t_plus_r_inv, void* const* out_w_plus_r_inv);
+// ppsnark's Spark representation of k resident matrices (ppsnark_key.hpp): row, col, one value vector per matrix, ts_row, ts_col, n elements
+// each; nnz[j]: the entry count of mats[j].  Outputs follow NMX_SCALARS_DEVICE, a NULL output is not computed; synchronous.  n, the shapes
+// and the overlaps are the caller's to check.
+void fv_ppsnark_spark_repr(Ctx&, int field, const CsrView* mats, const size_t* nnz, size_t k, size_t n, uint32_t flags, void* out_row,
+                           void* out_col, void* const* out_vals, void* out_ts_row, void* out_ts_col);
 // NeutronNova's folding step (neutron.hpp): the pow tables, the five sums of prove_helper (v8: E1, Az1, Bz1, Cz1, E2, Az2, Bz2, Cz2), the sum
 // of is_sat (v4: E, Az, Bz, Cz) and the witness fold.  Vectors follow NMX_SCALARS_DEVICE, tau / rho / r_b are host pointers; the two sums are
 // synchronous, the other two take NMX_ASYNC with HBM operands.  Shapes, NULLs and the scalars' range are the caller's to check.

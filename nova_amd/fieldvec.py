@@ -564,6 +564,44 @@ def ppsnark_mem_oracles(field, mems, addrs, Ls, tss, gamma, r, mont=False):
     return [tuple(outs[j][m][1] for j in range(4)) for m in range(k)]
 
 
+# ---- ppsnark's key tables (src/spartan/ppsnark.rs:117-190, src/spartan/polys/masked_eq.rs:57-75) ----------------------------------
+def ppsnark_spark_size(nnzs, num_vars, num_cons):
+    """N of R1CSShapeSparkRepr::new (ppsnark.rs:118-121): max(total entries, 2 num_vars, num_cons).next_power_of_two()."""
+    m = max(sum(nnzs), 2 * num_vars, num_cons, 1)
+    return 1 << (m - 1).bit_length()
+
+
+def ppsnark_spark_repr(mats, n, mont=False, device=True):
+    """R1CSShapeSparkRepr::new (ppsnark.rs:117-190) over resident SparseMatrix objects (the reference: A, B, C): returns (row, col, vals,
+    ts_row, ts_col), every vector n field elements and vals one vector per matrix -- CUDA tensors with device=True, numpy arrays otherwise.
+    n: a power of two, at least the total entry count and every matrix's rows and columns (ppsnark_spark_size gives the reference's)."""
+    import ctypes
+    k = len(mats)
+    hs = (ctypes.c_uint64 * max(k, 1))(*[m.handle for m in mats])
+    if device:
+        import torch
+        ref = torch.empty(0, dtype=torch.uint8, device="cuda")
+    else:
+        ref = None
+    outs = [_out_like(device, n, ref) for _ in range(4 + k)]
+    vals = (ctypes.c_void_p * max(k, 1))(*[o[0] for o in outs[2:2 + k]])
+    _check(L.lib().nmx_ppsnark_spark_repr(hs, k, n, _flags(device, mont), outs[0][0], outs[1][0], vals, outs[2 + k][0], outs[3 + k][0]))
+    return outs[0][1], outs[1][1], [o[1] for o in outs[2:2 + k]], outs[2 + k][1], outs[3 + k][1]
+
+
+def masked_eq_evals(field, r, num_masked_vars, mont=False, device=False):
+    """MaskedEqPolynomial::evals (masked_eq.rs:57-75): eq_evals_from_points(field, r) with the first 2^num_masked_vars entries zero."""
+    rr = _host_u8(r, 32)
+    ell = rr.size // 32
+    ref = None
+    if device:
+        import torch
+        ref = torch.empty(0, dtype=torch.uint8, device="cuda")
+    po, out = _out_like(device, 1 << ell, ref)
+    _check(L.lib().nmx_masked_eq_evals(field, rr.ctypes.data if ell else None, ell, num_masked_vars, _flags(device, mont), po))
+    return out
+
+
 # ---- Spartan's sum-check provers, one call each (nmx_sumcheck_prove_*; src/spartan/sumcheck.rs:199-507) ---------------------
 def as_transcript(fn):
     """fn(list of 32-byte coefficient strings) -> 32-byte challenge, wrapped as nmx_transcript_fn.  The transcript (Keccak on
