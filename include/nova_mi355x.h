@@ -162,6 +162,34 @@ int nmx_bases_read(uint64_t handle, size_t offset, size_t n, void* out_xy64);
  * src/provider/hyperkzg.rs:357-376, whose real keys come from the host). */
 int nmx_bases_generate(int curve, uint64_t k0, size_t n, uint32_t flags, uint64_t* handle);
 
+/* ---- fixed-base keys ----------------------------------------------------------------------------------
+ * The key HyperKZG users make first: CommitmentKey::setup_from_rng (src/provider/hyperkzg.rs:357-410, reached from
+ * CommitmentEngine::setup, :565-567) computes ck[i] = tau^i * G for n.next_power_of_two() points with setup_from_tau_direct, or
+ * with setup_from_tau_fixed_base_exp -> fixed_base_exp_comb_batch (:443-) from 100 000 points on.  Both calls below make such a
+ * key in HBM -- no N-sized host work, no upload -- as N fixed-base multiplications over ONE table T[w][d] = d * 2^(c w) * B of
+ * affine points (c = 8 by default: 32 x 255 points; nmx_set_option("fixed_base_c", 4..16)): a lane cuts its scalar into c-bit
+ * digits, adds one table entry per non-zero digit with no doubling, and a block of 256 lanes shares one inversion on the way to
+ * affine (nova_amd/csrc/fixed_base.hpp).  from_label (hash-to-curve for h) and tau_H on G2 stay on the host: one point each.
+ *  - nmx_bases_from_scalars: key[i] = scalars[i] * B.  B = base_xy64 (64 bytes, host, in the form NMX_BASES_MONT names), or the
+ *    curve's standard generator when NULL.
+ *  - nmx_bases_setup_from_tau: key[i] = tau^i * G, i in [0, n): setup_from_tau_direct / setup_from_tau_fixed_base_exp.  tau32: host,
+ *    32 bytes.  The host computes the 31 squarings tau^(2^j); lane i multiplies those the bits of i select.  The caller rounds n
+ *    (next_power_of_two) as the reference does.
+ * flags: NMX_SCALARS_MONT (the scalars and tau), NMX_SCALARS_DEVICE (from_scalars only: `scalars` is in HBM; such a key stays on
+ * logical device 0), NMX_BASES_MONT (the form of base_xy64; from_scalars only), NMX_BASES_PRECOMPUTE (window tables, as for
+ * nmx_bases_generate).
+ * Errors, with nothing registered and *handle untouched: NMX_E_ARG for n == 0 or n >= 2^31, a NULL handle, scalars or tau32, an
+ * unknown curve or a flag that does not apply; NMX_E_POINT for a base that is not canonical, is off the curve or is the identity;
+ * NMX_E_SCALAR_RANGE for a scalar or tau >= r (stored words, either form, as nmx_msm_handle treats scalars): tau and host scalars
+ * are checked on the host before anything is launched, HBM scalars by the kernel, which reads such a scalar as zero -- no table
+ * read depends on it -- and raises a flag.
+ * A scalar that is 0 mod r gives the identity, stored as the all-zero x || y; the key then counts as holding identity points, as a
+ * registered key with (0, 0) entries does, so MSMs over it stay correct.  The result is an ordinary key handle: nmx_bases_read,
+ * nmx_msm_handle, nmx_commit, nmx_bases_unregister, and sharding over the active devices as nmx_bases_generate (shard p of a tau key
+ * computes tau^(begin + i) from its own begin). */
+int nmx_bases_from_scalars(int curve, const void* base_xy64, const void* scalars, size_t n, uint32_t flags, uint64_t* handle);
+int nmx_bases_setup_from_tau(int curve, const void* tau32, size_t n, uint32_t flags, uint64_t* handle);
+
 /* ---- MSM ---------------------------------------------------------------------------------------------
  * DlogGroupExt::vartime_multiscalar_mul (src/provider/traits.rs:79; impls src/provider/bn256_grumpkin.rs:45-47,
  * src/provider/traits.rs:371-377) == msm() (src/provider/msm.rs:225-419):  out = sum_i scalars[i] * bases[i].
@@ -917,6 +945,8 @@ int nmx_set_window_bits(uint32_t c);
  * at tiny shapes),
  * "neutron_max_blocks" (the largest grid of nmx_neutron_fold_sums / nmx_neutron_relation_sum: 0 = by size, at most 2048; tests force a
  * wave's loop over several tiles at tiny shapes; never changes a result),
+ * "fixed_base_c" (window width of the table behind nmx_bases_from_scalars / nmx_bases_setup_from_tau: 4..16, default 8, other values:
+ * NMX_E_ARG; the table holds ceil(BITS / c) x (2^c - 1) points of 64 bytes; never changes a result),
  * "host_split" / "host_split_min_n" (an MSM with HOST scalars over at least host_split_min_n = 2^19 pairs of a key on one device is cut
  * into contiguous pieces (host_split = 255, the default: 2 / 3 / 4 pieces from 2^19 / 2^20 / 2^21 pairs; 2..16: that many) -- the
  * reference's own chunk + reduce decomposition, src/provider/msm.rs:564-574 -- so that piece i's scalars cross PCIe while piece

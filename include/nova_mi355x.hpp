@@ -74,6 +74,25 @@ class CommitmentKey {
     check(nmx_bases_read(k.handle_, n, 1, k.h_.data()));
     return k;
   }
+  // key[i] = scalars[i] * base made in HBM (nmx_bases_from_scalars); base == nullptr: the curve's generator.  mont names the form of the
+  // scalars, of *base and of h.
+  static CommitmentKey from_scalars(int curve, const std::vector<Scalar>& scalars, const Affine* base, const Affine& h, bool mont = false,
+                                    bool precompute = true) {
+    CommitmentKey k(curve, scalars.size(), h);
+    k.mont_ = mont;
+    const uint32_t flags = (mont ? (NMX_SCALARS_MONT | NMX_BASES_MONT) : 0u) | (precompute ? NMX_BASES_PRECOMPUTE : 0u);
+    check(nmx_bases_from_scalars(curve, base ? base->data() : nullptr, scalars.data(), scalars.size(), flags, &k.handle_));
+    return k;
+  }
+  // HyperKZG's key from a known tau (CommitmentKey::setup_from_rng, hyperkzg.rs:357-410): ck[i] = tau^i * G for n.next_power_of_two()
+  // points made in HBM (nmx_bases_setup_from_tau).  h (from_label) and tau_H (G2) stay the caller's.
+  static CommitmentKey setup_from_tau(int curve, size_t n, const Scalar& tau, const Affine& h, bool mont = false, bool precompute = true) {
+    CommitmentKey k(curve, next_power_of_two(n), h);
+    k.mont_ = mont;
+    const uint32_t flags = (mont ? NMX_SCALARS_MONT : 0u) | (precompute ? NMX_BASES_PRECOMPUTE : 0u);
+    check(nmx_bases_setup_from_tau(curve, tau.data(), k.n_, flags, &k.handle_));
+    return k;
+  }
   CommitmentKey(CommitmentKey&& o) noexcept : curve_(o.curve_), n_(o.n_), h_(o.h_), mont_(o.mont_), handle_(o.handle_) {
     o.handle_ = 0;
   }

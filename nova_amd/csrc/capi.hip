@@ -1517,6 +1517,62 @@ int nmx_bases_generate(int curve, uint64_t k0, size_t n, uint32_t flags, uint64_
   });
 }
 
+// ---- fixed-base keys (fixed_base.hpp; src/provider/hyperkzg.rs:357-410, :443-) ------------------------------------------------------------
+// Everything that can be refused without a device is refused before one is leased; *handle is written on success only.
+static void require_canonical(int field_id, const void* p, size_t count, const char* msg);
+static void fixed_base_checks(const uint64_t* handle, size_t n, uint32_t flags, uint32_t allowed, const char* what) {
+  require(handle != nullptr, NMX_E_ARG, "null argument");
+  require(n >= 1 && n < (1ull << 31), NMX_E_ARG, "n must be at least 1 and below 2^31");
+  require((flags & ~allowed) == 0, NMX_E_ARG, what);
+}
+int nmx_bases_from_scalars(int curve, const void* base_xy64, const void* scalars, size_t n, uint32_t flags, uint64_t* handle) {
+  return guarded([&] {
+    require(scalars != nullptr, NMX_E_ARG, "null argument");
+    fixed_base_checks(handle, n, flags, NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_BASES_MONT | NMX_BASES_PRECOMPUTE,
+                      "nmx_bases_from_scalars: only NMX_SCALARS_MONT, NMX_SCALARS_DEVICE, NMX_BASES_MONT and NMX_BASES_PRECOMPUTE apply");
+    const CurveOps& o = ops(curve);
+    uint8_t base[64];
+    if (base_xy64) {
+      require(o.check_point_host((const uint8_t*)base_xy64, flags, base), NMX_E_POINT, "the base is not canonical or not on the curve");
+      uint8_t any = 0;
+      for (int i = 0; i < 64; i++) any |= base[i];
+      require(any != 0, NMX_E_POINT, "the base is the identity");
+    }
+    const bool dev = (flags & NMX_SCALARS_DEVICE) != 0;
+    if (!dev) require_canonical(o.scalar_field, scalars, n, "scalar >= field modulus");
+    FixedBaseCall fc;
+    fc.base_xy64 = base_xy64 ? base : nullptr;
+    fc.scalars_device = dev, fc.scalars_mont = (flags & NMX_SCALARS_MONT) != 0;
+    fc.c = G.fixed_base_c.load(std::memory_order_relaxed);
+    CtxLease L;
+    // (a device-resident scalar array lives on one device: such keys stay whole)
+    *handle = publish(build_key(*L.c, curve, n, !dev, true, [&](Ctx& cx, BaseSet& part, size_t begin) {
+      FixedBaseCall pc = fc;
+      pc.scalars = (const char*)scalars + 32 * begin;
+      pc.begin = begin;
+      o.fixed_base(cx, part, pc, flags & NMX_BASES_PRECOMPUTE);
+    }));
+  });
+}
+int nmx_bases_setup_from_tau(int curve, const void* tau32, size_t n, uint32_t flags, uint64_t* handle) {
+  return guarded([&] {
+    require(tau32 != nullptr, NMX_E_ARG, "null argument");
+    fixed_base_checks(handle, n, flags, NMX_SCALARS_MONT | NMX_BASES_PRECOMPUTE,
+                      "nmx_bases_setup_from_tau: only NMX_SCALARS_MONT and NMX_BASES_PRECOMPUTE apply");
+    const CurveOps& o = ops(curve);
+    require_canonical(o.scalar_field, tau32, 1, "tau >= field modulus");
+    FixedBaseCall fc;
+    fc.tau32 = tau32, fc.scalars_mont = (flags & NMX_SCALARS_MONT) != 0;
+    fc.c = G.fixed_base_c.load(std::memory_order_relaxed);
+    CtxLease L;
+    *handle = publish(build_key(*L.c, curve, n, true, true, [&](Ctx& cx, BaseSet& part, size_t begin) {
+      FixedBaseCall pc = fc;
+      pc.begin = begin;  // shard p computes tau^(begin + i) from its own begin
+      o.fixed_base(cx, part, pc, flags & NMX_BASES_PRECOMPUTE);
+    }));
+  });
+}
+
 int nmx_msm_handle(uint64_t handle, size_t offset, const void* scalars, size_t n, uint32_t flags,
                    uint8_t* out, uint8_t* out_is_inf) {
   return guarded([&] {
@@ -3482,6 +3538,10 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "horner_sub") G.horner_sub = value;
     else if (n == "mercury_seg_rows") G.mercury_seg_rows = value;
     else if (n == "neutron_max_blocks") G.neutron_max_blocks = value;
+    else if (n == "fixed_base_c") {
+      require(value >= kFbMinC && value <= kFbMaxC, NMX_E_ARG, "fixed_base_c: window width of the fixed-base key kernels, 4 .. 16");
+      G.fixed_base_c = value;
+    }
     else if (n == "eq_max_blocks") G.eq_max_blocks = value;
     else if (n == "horner_spin_limit") G.horner_spin_limit = value;
     else if (n == "seg_heavy_above") G.seg_heavy_above = value > 63u ? 63u : value;

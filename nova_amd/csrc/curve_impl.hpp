@@ -635,6 +635,62 @@ template <int CID> struct CurveImpl {
     }
     bs.d = d;
   }
+  // key[i] = s_i * B (fixed_base.hpp): window bases on the host, the table, the multiplication with its block normalisation, then the
+  // key's own window tables as `generate` builds them.  One synchronisation reads the flag word before anything is kept.
+  static void fixed_base(Ctx& c, BaseSet& bs, const FixedBaseCall& fc, uint32_t flags) {
+    const size_t n = bs.n;
+    const uint32_t cw = fc.c, W = fb_windows(FpParams<SF>::BITS, cw);
+    const size_t entries = (size_t)W * fb_entries(cw);
+    Affine<BF> B;
+    if (fc.base_xy64) {
+      B.x = fp_from_bytes<BF>(fc.base_xy64).to_internal().canon();
+      B.y = fp_from_bytes<BF>(fc.base_xy64 + 32).to_internal().canon();
+    } else {
+      B.x = Fp<BF>::from_words(C::GX).to_internal().canon();
+      B.y = Fp<BF>::from_words(C::GY).to_internal().canon();
+    }
+    std::vector<AffineW> win(W);
+    fb_window_bases<BF>(B, cw, W, win.data());
+    FbMulArgs<SF> m{};
+    if (!fc.scalars) fb_tau_squarings<SF>(fc.tau32, fc.scalars_mont, m.sq);
+    void* d = nullptr;
+    table_shape<CID>(n, flags, &bs.pre_c, &bs.pre_W);
+    apply_table_limit(n, &bs.pre_c, &bs.pre_W);
+    HIPCHK(hipMalloc(&d, n * 64 * (bs.pre_W ? bs.pre_W : 1)));
+    try {
+      const bool stage = fc.scalars && !fc.scalars_device;
+      arena_reserve(c, 256 + pad256(W * 64) + pad256(entries * 64) + (stage ? pad256(n * 32) : 0));
+      DeviceBackend be(c, false, false);
+      uint32_t* dflags = be.alloc<uint32_t>(64);
+      AffineW* dwin = be.alloc<AffineW>(W);
+      AffineW* dtab = be.alloc<AffineW>(entries);
+      HIPCHK(hipMemsetAsync(dflags, 0, 4, c.stream));
+      HIPCHK(hipMemcpyAsync(dwin, win.data(), W * 64, hipMemcpyHostToDevice, c.stream));
+      be.launch_kernel(k_fb_table<BF>, (uint32_t)((entries + kFbThreads - 1) / kFbThreads), kFbThreads, FbTableArgs{dwin, dtab, dflags, cw, W});
+      m.table = dtab, m.out = (AffineW*)d, m.flags = dflags;
+      m.n = (uint32_t)n, m.c = cw, m.W = W, m.scalars_mont = fc.scalars_mont ? 1u : 0u, m.begin = (uint32_t)fc.begin;
+      if (stage) {
+        uint32_t* ds = be.alloc<uint32_t>(n * 8);
+        HIPCHK(hipMemcpyAsync(ds, fc.scalars, n * 32, hipMemcpyHostToDevice, c.stream));
+        m.scalars = ds;
+      } else {
+        m.scalars = (const uint32_t*)fc.scalars;
+      }
+      be.launch_kernel(k_fb_mul<BF, SF>, (uint32_t)((n + kFbThreads - 1) / kFbThreads), kFbThreads, m);
+      uint32_t hflags = 0;
+      HIPCHK(hipMemcpyAsync(&hflags, dflags, 4, hipMemcpyDeviceToHost, c.stream));
+      HIPCHK(hipStreamSynchronize(c.stream));
+      require(!(hflags & FB_ERR_SCALAR_RANGE), NMX_E_SCALAR_RANGE, "scalar >= field modulus");
+      build_tables<CID>(c, d, n, bs.pre_c, bs.pre_W);
+      HIPCHK(hipStreamSynchronize(c.stream));
+      bs.any_identity = (hflags & FB_ANY_IDENTITY) != 0;  // s_i = 0 mod r
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);
+      (void)hipFree(d);
+      throw;
+    }
+    bs.d = d;
+  }
   static void internal_to_canonical(uint8_t* e, size_t count) {
     for (size_t i = 0; i < count; i++) {
       Fp<BF> f = fp_from_bytes<BF>(e + 32 * i);
@@ -668,7 +724,7 @@ template <int CID> struct CurveImpl {
   }
   static CurveOps ops() {
     return CurveOps{&msm_key, &msm_key_batch, &batch_limit, &commit, &upload, &check_point_host, FpParams<BF>::PW,
-                    &generate, &internal_to_canonical, &point_sum, &blind_term, &check_layout, &table_bytes, &commit_batch, SF};
+                    &generate, &fixed_base, &internal_to_canonical, &point_sum, &blind_term, &check_layout, &table_bytes, &commit_batch, SF};
   }
 };
 

@@ -27,6 +27,7 @@
 #include "curves.hpp"
 #include "msm_pipeline.hpp"
 #include "curve_quad.hpp"
+#include "fixed_base.hpp"
 
 namespace nmx {
 
@@ -333,6 +334,7 @@ struct Global {
   std::atomic<uint32_t> horner_spin_limit{0};     // option horner_spin_limit: polls before a wave of the scan gives up (0 = 2^22; tests set 1 to force the fall-back)
   std::atomic<uint32_t> horner_window{64};        // option horner_window: tiles per look-back round of the single-pass scan (tests: 1 .. 63 force the multi-round path)
   std::atomic<uint32_t> mercury_seg_rows{0};      // option mercury_seg_rows: rows per segment of Mercury's division kernels (mercury.hpp mercury_plan; 0 = by size; tests force the multi-segment path at tiny shapes)
+  std::atomic<uint32_t> fixed_base_c{kFbDefaultC};         // option fixed_base_c: window width of the fixed-base key kernels (fixed_base.hpp; 4 .. 16, default 8: docs/measurements.md)
   std::atomic<uint32_t> neutron_max_blocks{0};    // option neutron_max_blocks: the largest grid of the two NeutronNova sums (neutron.hpp neutron_blocks; 0 = by size; tests force a wave's loop over tiles at tiny shapes)
   std::atomic<uint32_t> seg_heavy_above{0};       // env NMX_TUNE_SEG_HEAVY_ABOVE / option seg_heavy_above: 0 = by pieces per bucket (8 or 12)
   std::atomic<uint32_t> prefix_tables{2};         // env NMX_TUNE_PREFIX_TABLES / option prefix_tables: narrower table sets over a key's first points (capi.hip add_prefix_tables): 0 none, 1 the 2^18-point set of wide-table keys only, 2 the whole chain (batches descend it)
@@ -730,6 +732,16 @@ struct BatchItem {
 // through pinned staging buffers (keyfile.hip)
 using BaseFill = std::function<void(void* d_dst, hipStream_t stream)>;
 
+// one fixed-base key (fixed_base.hpp): part.n points s_i * B, i counted from `begin` of the whole key
+struct FixedBaseCall {
+  const uint8_t* base_xy64 = nullptr;  // host, canonical x || y, on the curve and not the identity (checked by the caller); null: the generator
+  const void* scalars = nullptr;       // this part's scalars, host or device; null: tau mode
+  bool scalars_device = false, scalars_mont = false;  // (scalars_mont also names tau's form)
+  const void* tau32 = nullptr;         // host, below r (checked by the caller)
+  size_t begin = 0;                    // tau mode: point i of the part is tau^(begin + i) * B
+  uint32_t c = 8;                      // window width, 4 .. 16
+};
+
 struct CurveOps {
   // out = sum scalars[i] * key[offset + i], i < n, through the key's window tables when it has them
   void (*msm_key)(Ctx&, const BaseSet&, size_t offset, size_t n, const MsmCall&, uint32_t flags, uint8_t* out,
@@ -749,6 +761,9 @@ struct CurveOps {
   bool (*check_point_host)(const uint8_t* xy64, uint32_t flags, uint8_t* out_canonical_xy64);
   const uint32_t* base_modulus_words;  // 8 x u32
   void (*generate)(Ctx&, BaseSet& bs, uint64_t k0, uint32_t flags);
+  // fill bs as `generate` does, with bs.n fixed-base multiples; flags: NMX_BASES_PRECOMPUTE.  NMX_E_SCALAR_RANGE (nothing kept) when a
+  // device scalar is not below r
+  void (*fixed_base)(Ctx&, BaseSet& bs, const FixedBaseCall&, uint32_t flags);
   void (*internal_to_canonical)(uint8_t* elems32, size_t count);  // host, in place
   // host: sum of 128-byte partials -> affine point, or (flags & NMX_OUT_PARTIAL) one more partial
   void (*point_sum)(const uint8_t* partials128, size_t count, uint32_t flags, uint8_t* out, uint8_t* inf);

@@ -235,6 +235,30 @@ class CommitmentKey:
         key.h = key.read(n, 1).tobytes()
         return key
 
+    @classmethod
+    def from_scalars(cls, curve, scalars, base=None, h_xy64=None, mont=False, precompute=True):
+        """key[i] = scalars[i] * base, made in HBM (nmx_bases_from_scalars); base=None: the curve's generator.  scalars: (n, 32) uint8 on the
+        host or a CUDA tensor (used in place).  mont names the form of the scalars, of base and of h_xy64."""
+        sp, n, dev, _keep = _scalar_arg(scalars, 32)
+        b = None if base is None else _host_u8(base, 64)
+        h = ctypes.c_uint64(0)
+        flags = dev | ((L.SCALARS_MONT | L.BASES_MONT) if mont else 0) | (L.BASES_PRECOMPUTE if precompute else 0)
+        _check(L.lib().nmx_bases_from_scalars(curve, None if b is None else b.ctypes.data, sp, n, flags, ctypes.byref(h)))
+        return cls(curve, h.value, n, h_xy64 if h_xy64 is not None else bytes(64), mont)
+
+    @classmethod
+    def setup_from_tau(cls, curve, n, tau, h_xy64=None, mont=False, precompute=True):
+        """HyperKZG's key from a known tau (CommitmentKey::setup_from_rng, src/provider/hyperkzg.rs:357-410): ck[i] = tau^i * G for
+        n.next_power_of_two() points, made in HBM (nmx_bases_setup_from_tau).  tau: 32 bytes; mont names its form and that of h_xy64.
+        `h` (from_label on the reference side) and tau_H (G2) stay with the host."""
+        num = 1 if n <= 1 else 1 << (n - 1).bit_length()
+        t = _host_u8(tau, 32)
+        assert t.size == 32, "tau is one scalar"
+        h = ctypes.c_uint64(0)
+        flags = (L.SCALARS_MONT if mont else 0) | (L.BASES_PRECOMPUTE if precompute else 0)
+        _check(L.lib().nmx_bases_setup_from_tau(curve, t.ctypes.data, num, flags, ctypes.byref(h)))
+        return cls(curve, h.value, num, h_xy64 if h_xy64 is not None else bytes(64), mont)
+
     def shard_plan(self, offset=0, n=None):
         """[(device, offset inside the shard, count)] for a call over key[offset, offset + n), from the layout the
         REGISTERED key has (nmx_bases_shard_plan) -- the plan to cut shard-resident scalar pieces by.  (A generated key is
@@ -388,6 +412,10 @@ class CommitmentEngine:
 
     def setup_synthetic(self, n, k0=1):
         return CommitmentKey.generate(self.group.curve, n, k0)
+
+    def setup_from_tau(self, n, tau, h_xy64=None, mont=False, precompute=True):
+        """`CommitmentEngine::setup` with tau known (src/provider/hyperkzg.rs:565-567 -> :357-410): see CommitmentKey.setup_from_tau"""
+        return CommitmentKey.setup_from_tau(self.group.curve, n, tau, h_xy64, mont, precompute)
 
     def commit(self, ck, v, r=None, mont=False, partial=False):
         """msm(v, ck[..len v]) + h*r  (pedersen.rs:263-270, hyperkzg.rs:584-591).  v may be a ShardedVector."""
