@@ -957,6 +957,8 @@ int nmx_set_window_bits(uint32_t c);
  * reduction: 0 = fused levels or one launch per level by the box's measured launch gap, 1 = one launch per level, 2 = fused),
  * "reduce_form" (bucket reduction: 0 = by bucket count, 1 = the (D, Y) pair tree, 2 = bit-sliced sums -- the pair-sum tree, the sums of
  * its odd nodes per level and one pairwise combine at the end; other values: NMX_E_ARG),
+ * "host_combine" (that combine at the end of the bit-sliced sums: 0 = by rule, 1 = in the reduction's last launch, 2 = on the calling
+ * host thread wherever the c points of every bucket set fit the call's 64 KiB landing buffer; other values: NMX_E_ARG),
  * "no_clean_accum" (1: keys without identity points also run the segment accumulate that tests every gathered row for the identity),
  * "hist_grid" (blocks of the partition's counting pass; 0 = as the placing pass: measured flat, profiles/r03_msm_2p20/tail_ab.txt),
  * "shard_min_n", "cache_table_after", "max_table_mib" (see the sections above), "force_peer_copy" (1: the HBM-resident scalars of

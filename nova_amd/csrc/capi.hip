@@ -166,6 +166,11 @@ static void ensure_init() {
     require(v >= 0 && v <= 2, NMX_E_ARG, "NMX_TUNE_REDUCE_FORM: 0 = by bucket count, 1 = pair tree, 2 = bit-sliced sums");
     G.reduce_form = (uint32_t)v;
   }
+  if (const char* t = getenv("NMX_TUNE_HOST_COMBINE")) {
+    const int v = atoi(t);
+    require(v >= 0 && v <= 2, NMX_E_ARG, "NMX_TUNE_HOST_COMBINE: 0 = by rule, 1 = the device combines, 2 = the host wherever the slices fit");
+    G.host_combine = (uint32_t)v;
+  }
   if (const char* t = getenv("NMX_TUNE_TREE_THREADS")) G.tree_threads = (uint32_t)atoi(t);
   if (const char* t = getenv("NMX_TUNE_BIG_SLICE")) G.big_slice = (uint32_t)atoi(t);
   if (const char* t = getenv("NMX_TUNE_BIG_THREADS")) G.big_threads = (uint32_t)atoi(t);
@@ -3504,6 +3509,10 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "reduce_form") {
       require(value <= 2, NMX_E_ARG, "reduce_form: 0 = by bucket count, 1 = pair tree, 2 = bit-sliced sums");
       G.reduce_form = value;
+    }
+    else if (n == "host_combine") {
+      require(value <= 2, NMX_E_ARG, "host_combine: 0 = by rule, 1 = the device combines, 2 = the host wherever the slices fit");
+      G.host_combine = value;
     }
     else if (n == "big_slice") G.big_slice = value;
     else if (n == "big_threads") G.big_threads = value;

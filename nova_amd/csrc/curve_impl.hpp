@@ -105,7 +105,7 @@ template <int CID> struct GenFn {  // P_i = (k0 + i) * G
 // ---------------------------------------------------------------------------------------------------
 static inline uint64_t shape_hash(const MsmArgs& a, const MsmCall& mc, size_t sbytes, uint32_t cid, uint32_t sbits,
                                   uint32_t seg_lanes) {
-  const uint64_t v[11] = {((uint64_t)cid << 56) | ((uint64_t)sbits << 40) | seg_lanes, a.n, a.u64_bits | ((uint64_t)((G.no_tree_fuse.load(std::memory_order_relaxed) & 15u) | (G.reduce_form.load(std::memory_order_relaxed) << 4)) << 32) | ((uint64_t)G.tree_threads.load(std::memory_order_relaxed) << 40) | ((uint64_t)a.big_slice << 44), a.force_c, a.force_lmax, a.force_fold_t, ((uint64_t)a.pre_stride << 8) | a.pre_c,
+  const uint64_t v[11] = {((uint64_t)cid << 56) | ((uint64_t)sbits << 40) | seg_lanes, a.n, a.u64_bits | ((uint64_t)((G.no_tree_fuse.load(std::memory_order_relaxed) & 15u) | (G.reduce_form.load(std::memory_order_relaxed) << 4) | (G.host_combine.load(std::memory_order_relaxed) << 6)) << 32) | ((uint64_t)G.tree_threads.load(std::memory_order_relaxed) << 40) | ((uint64_t)a.big_slice << 44), a.force_c, a.force_lmax, a.force_fold_t, ((uint64_t)a.pre_stride << 8) | a.pre_c,
                           (uint64_t)(mc.gather_host != nullptr) | (mc.all_ones ? 2u : 0u) | (mc.scalars_device ? 4u : 0u) |
                               (a.no_partition ? 8u : 0u),
                           sbytes, a.seg_min_total, G.seg_lanes_override ^ ((uint64_t)a.seg_heavy_above << 32)};

@@ -125,6 +125,17 @@ inline MsmShape make_shape(uint32_t n, uint32_t bits, uint32_t force_c, uint32_t
   return sh;
 }
 
+// A backend whose reduction can end in slices instead of sums (DeviceBackend: slice_recs, d2h_slices) brings them to the host
+// and finishes them inside its sync(); every other backend returns sums.  true: the copy is enqueued.
+template <int FID, class BE>
+auto slices_to_host(BE& be, XYZZW* wsum_host, uint32_t WB, uint32_t* err_host, const XYZZW* Y, int)
+    -> decltype(be.template d2h_slices<FID>(wsum_host, WB, err_host, Y), bool()) {
+  if (!be.slice_recs) return false;
+  be.template d2h_slices<FID>(wsum_host, WB, err_host, Y);
+  return true;
+}
+template <int FID, class BE> bool slices_to_host(BE&, XYZZW*, uint32_t, uint32_t*, const XYZZW*, long) { return false; }
+
 // Runs stages 1-7.  On return `wsum_host[0..WB)` holds the per-window sums (XYZZ, Montgomery), and *err_host the
 // device error bits.  Returns the shape used.
 template <class BE, int FID, int SFID>
@@ -378,7 +389,9 @@ MsmShape msm_pipeline(BE& be, const MsmArgs& a, uint32_t scalar_bits, XYZZW* wsu
   bool err_appended = false;  // the last tree launch parks the error word behind the sums: one copy instead of two
   const XYZZW* Y = be.template reduce_tree<FID>(buckets, sh, counters + 2, &err_appended);
   be.mark("tail");
-  if (err_appended) {
+  if (err_appended && slices_to_host<FID>(be, wsum_host, sh.WB, err_host, Y, 0)) {
+    // the reduction left slices: they and the error word come over in one copy, be.sync() combines them into wsum_host
+  } else if (err_appended) {
     be.d2h_split(wsum_host, sizeof(XYZZW) * sh.WB, err_host, sizeof(uint32_t), Y);
   } else {
     be.d2h(wsum_host, Y, sizeof(XYZZW) * sh.WB);

@@ -120,6 +120,9 @@ struct BsTreeArgs {
   XYZZW* out;         // last: the WB sums (block w writes set w's), the error word behind them
   uint32_t n_tot, S, levels, n_cont, last, WB;
   const uint32_t* err_src;  // last: the pipeline's error word
+  // last, 1: no combine.  Block w leaves its L + 1 points, canonical, at out[w (L + 1) ..]: the root, then O_0 .. O_(L-1); the
+  // error word sits behind all WB (L + 1) of them.  The host finishes (host_point4.hpp combine_slices).
+  uint32_t slices = 0;
 };
 // P: V (what a group holds of a point), groups() / group() / block(), load / store (canonical, memory), lds_load / lds_store
 // (raw limbs, point index into a buffer of 36-word points), add / dbl / ident, sync() (every thread of the block), lead() (one
@@ -130,7 +133,8 @@ template <class P> NMX_HD void bs_tree_body(P& p, const BsTreeArgs& a) {
   const uint32_t base = p.block() * a.S;
   const uint32_t A_in = a.n_cont + (a.view ? 1u : 0u);
   uint32_t* const buf[2] = {p.lds(), p.lds() + kBsBuf0 * 36u};
-  if (a.last && a.err_src && p.block() == 0 && p.lead()) *(uint32_t*)(a.out + a.WB) = *a.err_src;
+  const uint32_t recs = a.slices ? A_in + a.levels : 1u;  // records a set leaves in the last launch: L + 1 slices, or its sum
+  if (a.last && a.err_src && p.block() == 0 && p.lead()) *(uint32_t*)(a.out + (size_t)a.WB * recs) = *a.err_src;
   const uint32_t n_out = a.n_tot >> a.levels, base_out = base >> a.levels;
   for (uint32_t k = 1; k <= a.levels; k++) {
     const uint32_t A = A_in + k - 1u, cnt = a.S >> k;
@@ -168,6 +172,10 @@ template <class P> NMX_HD void bs_tree_body(P& p, const BsTreeArgs& a) {
   const uint32_t* const fin = buf[(a.levels - 1u) & 1u];
   uint32_t* const scr = buf[a.levels & 1u];
   const uint32_t L = A_in + a.levels - 1u;  // <= 31
+  if (a.slices) {
+    if (qd <= L) p.store(a.out, (size_t)p.block() * (L + 1u) + qd, p.lds_load(fin, qd));
+    return;
+  }
   uint32_t T = 0;
   while ((1u << T) < L) T++;
   // Groups L <= i < 2^T hold ident(): add() and dbl() must treat it as the group identity (the device's is the all-zero coordinate

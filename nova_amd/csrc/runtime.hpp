@@ -28,6 +28,7 @@
 #include "msm_pipeline.hpp"
 #include "curve_quad.hpp"
 #include "fixed_base.hpp"
+#include "host_point4.hpp"
 
 namespace nmx {
 
@@ -345,7 +346,8 @@ struct Global {
   std::atomic<uint32_t> no_tree_fuse{0};          // env NMX_TUNE_NO_TREE_FUSE / option no_tree_fuse: 0 / 2 = fused reduction tree (default), 1 = one launch per reduction level
   std::atomic<uint32_t> no_clean_accum{0};        // env NMX_TUNE_NO_CLEAN_ACCUM / option no_clean_accum: 1 = keys without identity points also run the segment accumulate that tests every row for the identity (A/B runs)
   std::atomic<uint32_t> reduce_form{0};           // env NMX_TUNE_REDUCE_FORM / option reduce_form: the bucket reduction: 0 = by bucket count, 1 = pair tree (ReducePairFn / k_reduce_tree), 2 = bit-sliced sums (reduce_bitsliced.hpp)
-  std::atomic<uint32_t> hist_grid{0};             // env NMX_TUNE_HIST_GRID / option hist_grid
+  std::atomic<uint32_t> host_combine{0};          // env NMX_TUNE_HOST_COMBINE / option host_combine: the end of the bit-sliced reduction, root + sum_l 2^l O_l: 0 = by rule (DeviceBackend::reduce_bitsliced), 1 = on the device (the last launch combines), 2 = on the host wherever the slices fit the landing buffer (host_point4.hpp combine_slices)
+  std::atomic<uint32_t> hist_grid{0};            // env NMX_TUNE_HIST_GRID / option hist_grid
   std::atomic<uint32_t> hist_bs{0};               // env NMX_TUNE_HIST_BS / option hist_bs: threads per block of k_hist_hi (0: as k_part_hi)
   std::atomic<uint32_t> horner_order{1};          // option horner_order: 1 = tiles of k_horner_scan by start-order ticket, 0 = by block id
   std::atomic<uint32_t> host_split{255};           // option host_split: a call with HOST scalars over >= host_split_min_n pairs of a single-device key is cut into this many pieces whose uploads overlap the previous piece's MSM (0 / 1: off)
@@ -552,22 +554,42 @@ struct DeviceBackend {
   //   2^16 (c = 17)              149 -> 133-135 us  with 128 (64: 142-157 us -- twice the blocks, or three one-step launches more)
   //   2^19 (c = 20)              374 -> 345 us      with 128
   // Bucket counts in between (forced window widths only) take the neighbouring rule; below 2^14 they were not measured and keep
-  // the pair tree.
+  // the pair tree -- while the DEVICE combines.
+  //
+  // The end of the reduction, root + sum_l 2^l O_l, is c - 2 dependent doublings on one block per bucket set: the last launch
+  // takes 68-80 us with it and 17.6 without at c = 17 (profiles/host_combine/reduce_launches_{parent,new}.txt).  Option host_combine: 1 = the last launch
+  // combines, 2 = it leaves every set's L + 1 points, which come over in the call's one copy and are combined on the calling
+  // thread behind the call's one wait (host_point4.hpp combine_slices, 12-18 us per set at L = 16), wherever the records fit the
+  // landing buffer; 0 = by rule (profiles/host_combine/: ab_pairs.txt, ab_sets.txt, ab_buckets.txt; wall clock per MSM, device ->
+  // host combine, alternating in one process):
+  //   bucket sets (fused batch over a 2^14-point key)   1: 246 -> 199 us   2: 287 -> 248   4: 377 -> 348   8: 487 -> 492   16: 744 -> 818
+  //       the host's cost grows with the sets, the device runs a block per set side by side: the host up to kHostCombineMaxSets = 4
+  //   buckets, one set, pair tree -> bit-sliced + host   128: 160 -> 138 us   2^14: 247 -> 188   2^15: 383 -> 328   2^16: 1 369 -> 1 311
+  //       2^19: 5 001 -> 4 830.  Without its combine the bit-sliced form also wins at 128 buckets (7 dependent additions against the
+  //       pair tree's 14): where the host combines it runs from kBitslicedHostFromM = 128 buckets on (counts in between: forced
+  //       window widths only, the neighbouring rule); below 128 nothing was measured and the pair tree stays.
   static constexpr uint32_t kBitslicedFromM = 1u << 14, kBitslicedFullBlocksFromM = 1u << 16, kBitslicedWideAbove = 32768;
+  static constexpr uint32_t kHostCombineMaxSets = 4, kBitslicedHostFromM = 128;
+  uint32_t slice_recs = 0;  // records per bucket set the last bit-sliced launch leaves for the host (L + 1); 0: it combined
+  static constexpr size_t slice_bytes(uint32_t WB, uint32_t recs) { return (size_t)WB * recs * sizeof(XYZZW) + sizeof(uint32_t); }
   template <int FID> const XYZZW* reduce_bitsliced(const XYZZW* buckets, const MsmShape& sh, const uint32_t* err_src, bool* err_appended) {
-    const uint32_t form = G.reduce_form.load(std::memory_order_relaxed);
-    if (form == 1 || (form == 0 && sh.M < kBitslicedFromM)) return nullptr;
+    const uint32_t form = G.reduce_form.load(std::memory_order_relaxed), hc = G.host_combine.load(std::memory_order_relaxed);
+    const uint32_t L = ilog2_u32(sh.M);
+    const bool host = hc != 1 && slice_bytes(sh.WB, L + 1) <= kPinnedBytes && (hc == 2 || sh.WB <= kHostCombineMaxSets);
+    if (form == 1 || (form == 0 && sh.M < (host ? kBitslicedHostFromM : kBitslicedFromM))) return nullptr;
     BsLaunch plan[kBsMaxLaunches];
     uint32_t n = 0;
     // the kernel's LDS always fits (at most 128 additions in a block's first level); what can fail is the 2^31 / 2^30 index range
     // of a launch and the launch count
     if (!bs_plan(sh.M, sh.WB, sh.M < kBitslicedFullBlocksFromM ? 64u : 128u, kBitslicedWideAbove, plan, &n)) return nullptr;
+    const uint32_t recs = host ? L + 1 : 1;
+    slice_recs = host ? recs : 0;
     const XYZZW* in = buckets;
     const XYZZW* prev_in = nullptr;
     for (uint32_t i = 0; i < n; i++) {
       const BsLaunch& l = plan[i];
       const XYZZW* view = l.view ? prev_in : nullptr;
-      XYZZW* out = l.last ? alloc<XYZZW>(sh.WB + 1)  // + the error word
+      XYZZW* out = l.last ? alloc<XYZZW>((size_t)sh.WB * recs + 1)  // + the error word
                           : alloc<XYZZW>((size_t)bs_out_arrays(l) * bs_out_elems(l));
       if (!dry) {
         if (l.wide) {
@@ -576,7 +598,8 @@ struct DeviceBackend {
           if (items < kQuadBelowItems) launch(BsStepQuadFn<FID>{a}, items * 4);
           else launch(BsStepFn<FID>{a}, items);
         } else {
-          const BsTreeArgs a{in, view, out, l.n_tot, l.S, l.levels, l.n_cont, l.last, sh.WB, l.last ? err_src : nullptr};
+          const BsTreeArgs a{in, view, out, l.n_tot, l.S, l.levels, l.n_cont, l.last, sh.WB, l.last ? err_src : nullptr,
+                             l.last && slice_recs ? 1u : 0u};
           hipLaunchKernelGGL((k_reduce_bitsliced<FID>), dim3(l.n_tot / l.S), dim3(kBsQuads * 4), 0, c.stream, a);
           HIPCHK(hipGetLastError());
         }
@@ -685,10 +708,32 @@ struct DeviceBackend {
       d2h(dst2, (const char*)src + bytes1, bytes2);
     }
   }
+  // The slices of the last bit-sliced launch (slice_recs records per set) and the error word behind them, in ONE copy; sync()
+  // combines every set's records on the calling thread into sums[w].  reduce_bitsliced() checked that they fit.
+  struct SliceFinish {
+    void (*combine)(const XYZZW*, uint32_t, XYZZW*);
+    size_t off;
+    uint32_t WB, recs;
+    XYZZW* sums;
+  };
+  std::vector<SliceFinish> finishes;
+  template <int FID> void d2h_slices(XYZZW* sums, uint32_t WB, uint32_t* err, const XYZZW* src) {
+    if (dry) return;
+    const size_t bytes = slice_bytes(WB, slice_recs);
+    if (!c.pinned) HIPCHK(hipHostMalloc((void**)&c.pinned, kPinnedBytes, hipHostMallocDefault));
+    require(pinned_used + bytes <= kPinnedBytes, NMX_E_HIP, "slices of the bucket reduction do not fit the landing buffer");
+    HIPCHK(hipMemcpyAsync(c.pinned + pinned_used, src, bytes, hipMemcpyDeviceToHost, c.stream));
+    finishes.push_back({&combine_slices<FID>, pinned_used, WB, slice_recs, sums});
+    landings.push_back({err, pinned_used + bytes - sizeof(uint32_t), sizeof(uint32_t)});
+    pinned_used += (bytes + 63) & ~(size_t)63;
+  }
   void sync() {
     if (dry) return;
     stream_wait(c.stream);
     for (const Landing& l : landings) memcpy(l.dst, c.pinned + l.off, l.bytes);
+    for (const SliceFinish& f : finishes)
+      for (uint32_t w = 0; w < f.WB; w++) f.combine((const XYZZW*)(c.pinned + f.off) + (size_t)w * f.recs, f.recs - 1, f.sums + w);
+    finishes.clear();
     landings.clear();
     pinned_used = 0;
   }
