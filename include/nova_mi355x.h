@@ -960,6 +960,9 @@ int nmx_set_window_bits(uint32_t c);
  * "host_combine" (that combine at the end of the bit-sliced sums: 0 = by rule, 1 = in the reduction's last launch, 2 = on the calling
  * host thread wherever the c points of every bucket set fit the call's 64 KiB landing buffer; other values: NMX_E_ARG),
  * "no_clean_accum" (1: keys without identity points also run the segment accumulate that tests every gathered row for the identity),
+ * "accum_prio" (progress-keyed wave priority in the segment accumulate: 0 = by rule, 1 = off, 2 = on -- a wave starts at priority 3 and
+ * steps down after a half, three quarters and seven eighths of its segment --, 3 = on with steps after equal quarters; other values:
+ * NMX_E_ARG; ignored where the segment accumulate does not run),
  * "hist_grid" (blocks of the partition's counting pass; 0 = as the placing pass: measured flat, profiles/r03_msm_2p20/tail_ab.txt),
  * "shard_min_n", "cache_table_after", "max_table_mib" (see the sections above), "force_peer_copy" (1: the HBM-resident scalars of
  * a sharded call are staged through hipMemcpyPeerAsync even when the shard sits on the source GPU: exercises the cross-device

@@ -195,6 +195,11 @@ static void ensure_init() {
   if (const char* t = getenv("NMX_TUNE_EQ_MAX_BLOCKS")) G.eq_max_blocks = (uint32_t)atoi(t);
   if (const char* t = getenv("NMX_TUNE_SEG_HEAVY_ABOVE")) G.seg_heavy_above = (uint32_t)atoi(t);
   if (const char* t = getenv("NMX_TUNE_ACCUM_PF")) G.accum_prefetch = (uint32_t)atoi(t);
+  if (const char* t = getenv("NMX_TUNE_ACCUM_PRIO")) {
+    const int v = atoi(t);
+    require(v >= 0 && v <= 3, NMX_E_ARG, "NMX_TUNE_ACCUM_PRIO: 0 = by rule, 1 = off, 2 = on, 3 = on with equal quarters");
+    G.accum_prio = (uint32_t)v;
+  }
   HIPCHK(hipSetDevice(dev));
   cache_init_defaults();
   if (const char* t = getenv("NMX_DEVICES")) {  // same as nmx_init_devices(k, 0), for hosts that cannot call it
@@ -3486,6 +3491,16 @@ int nmx_set_window_bits(uint32_t c) {
   return NMX_OK;
 }
 
+#if defined(NMX_ACCUM_TRACE)
+// Measuring build only (scripts/accum_wave_trace.py; not in the header): device memory that the segment accumulate of the MSMs
+// after this call writes four 64-bit words per wave into (msm_seg.hpp AccumTrace); null: stop.
+extern "C" int nmx_accum_trace_buffer(uint64_t* dev_buf, uint64_t words) {
+  G.accum_trace_buf = dev_buf;
+  G.accum_trace_words = dev_buf ? words : 0;
+  return NMX_OK;
+}
+#endif
+
 int nmx_set_option(const char* name, uint32_t value) {
   return guarded([&] {
     require(name != nullptr, NMX_E_ARG, "null argument");
@@ -3501,6 +3516,10 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "small_blocks") G.small_blocks = value;
     else if (n == "quad_final_below") G.quad_final_below = value;
     else if (n == "accum_prefetch") G.accum_prefetch = value;
+    else if (n == "accum_prio") {
+      require(value <= 3, NMX_E_ARG, "accum_prio: 0 = by rule, 1 = off, 2 = on, 3 = on with equal quarters");
+      G.accum_prio = value;
+    }
     else if (n == "no_batch_fuse") G.no_batch_fuse = value;
     else if (n == "prefix_tables") G.prefix_tables = value > 2 ? 2u : (uint32_t)value;
     else if (n == "no_tree_fuse") G.no_tree_fuse = value;

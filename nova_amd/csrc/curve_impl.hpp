@@ -108,7 +108,7 @@ static inline uint64_t shape_hash(const MsmArgs& a, const MsmCall& mc, size_t sb
   const uint64_t v[11] = {((uint64_t)cid << 56) | ((uint64_t)sbits << 40) | seg_lanes, a.n, a.u64_bits | ((uint64_t)((G.no_tree_fuse.load(std::memory_order_relaxed) & 15u) | (G.reduce_form.load(std::memory_order_relaxed) << 4) | (G.host_combine.load(std::memory_order_relaxed) << 6)) << 32) | ((uint64_t)G.tree_threads.load(std::memory_order_relaxed) << 40) | ((uint64_t)a.big_slice << 44), a.force_c, a.force_lmax, a.force_fold_t, ((uint64_t)a.pre_stride << 8) | a.pre_c,
                           (uint64_t)(mc.gather_host != nullptr) | (mc.all_ones ? 2u : 0u) | (mc.scalars_device ? 4u : 0u) |
                               (a.no_partition ? 8u : 0u),
-                          sbytes, a.seg_min_total, G.seg_lanes_override ^ ((uint64_t)a.seg_heavy_above << 32)};
+                          sbytes, a.seg_min_total, G.seg_lanes_override ^ ((uint64_t)a.seg_heavy_above << 32) ^ ((uint64_t)a.accum_prio << 40)};
   uint64_t h = 0x9e3779b97f4a7c15ull;
   for (uint64_t x : v) {
     h = (h ^ x) * 0xff51afd7ed558ccdull;
@@ -147,6 +147,11 @@ static XYZZ<CurveT<CID>::BF> run_msm(Ctx& c, const void* d_bases, size_t n, cons
   a.hist_grid = G.hist_grid;
   a.hist_bs = G.hist_bs;
   a.accum_clean = G.no_clean_accum.load(std::memory_order_relaxed) ? 0u : 1u;
+  a.accum_prio = accum_prio_sched((size_t)a.n * 16);  // the estimate seg_lanes() is asked with below
+#if defined(NMX_ACCUM_TRACE)
+  a.trace_buf = G.accum_trace_buf.load(std::memory_order_relaxed);
+  a.trace_words = G.accum_trace_words.load(std::memory_order_relaxed);
+#endif
   // gathers in flight per lane: one is enough while the key's tables (W x 64 B per point) mostly hit the 256 MB Infinity Cache
   // and L2; from ~6 GiB of tables on the gather latency shows and a second row in flight pays (2^24: accumulate 17.6 ->
   // 16.0 ms; neutral at 2^22, slightly worse at 2^20 / 2^21: profiles/r02_msm_2p20/prefetch_depth.txt)
@@ -423,6 +428,11 @@ static void run_msm_batch(Ctx& c, const BaseSet& bs, size_t offset, const BatchI
   a.hist_grid = G.hist_grid;
   a.hist_bs = G.hist_bs;
   a.accum_clean = G.no_clean_accum.load(std::memory_order_relaxed) ? 0u : 1u;
+  a.accum_prio = accum_prio_sched((size_t)a.n * 16);  // the estimate seg_lanes() is asked with below
+#if defined(NMX_ACCUM_TRACE)
+  a.trace_buf = G.accum_trace_buf.load(std::memory_order_relaxed);
+  a.trace_words = G.accum_trace_words.load(std::memory_order_relaxed);
+#endif
   {
     const uint32_t pf = G.accum_prefetch.load(std::memory_order_relaxed);
     a.accum_prefetch = pf ? pf : 1u;

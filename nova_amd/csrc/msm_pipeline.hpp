@@ -5,6 +5,7 @@
 //   HostEmulBackend (tests/host_emul) plain loops + std::sort, g++ only     -> indexing debug aid in tests
 #pragma once
 #include <stddef.h>
+#include <type_traits>
 #include "msm_partition.hpp"
 #include "msm_seg.hpp"
 
@@ -32,6 +33,11 @@ struct MsmArgs {
   uint32_t seg_min_len = 8;           // shortest segment a lane is given
   uint32_t accum_clean = 1;           // 0: keys without identity points run the testing instantiation too (option no_clean_accum: A/B)
   uint32_t accum_prefetch = 1;        // gathers in flight ahead of the addition (AccumSegFn PF)
+  uint32_t accum_prio = 0;            // 0: every wave of the segment accumulate at priority 0; else progress-keyed priority with these thresholds (AccumSegFn PRIO, prio_sched)
+#if defined(NMX_ACCUM_TRACE)
+  uint64_t* trace_buf = nullptr;      // measuring build: four words per wave of the segment accumulate (msm_seg.hpp AccumTrace)
+  uint64_t trace_words = 0;
+#endif
   uint32_t hist_grid = 0;             // blocks of the first-level counting pass (0: as many as the placing pass; tuning)
   uint32_t hist_bs = 0;               // threads per block of the counting pass (0: as the placing pass; it stages nothing, so any multiple of 64 >= the bin count works)
   uint32_t big_slice = 0;             // pieces per block of the big-bucket pass (< 32: SegPlan::big_slice_for)
@@ -310,15 +316,25 @@ MsmShape msm_pipeline(BE& be, const MsmArgs& a, uint32_t scalar_bits, XYZZW* wsu
     auto accum_seg = [&](auto fn) {
       decltype(fn) f{(const AffineW*)a.bases, vals1, start, end, total_p, bucket_raw, partial_raw, sh.nbuckets,
                      seg_lanes, a.seg_min_len, plan};
+      if (a.accum_prio) f.prio_sched = a.accum_prio;
+#if defined(NMX_ACCUM_TRACE)
+      f.trace = AccumTrace{a.trace_buf, a.trace_words};
+#endif
       be.launch(f, seg_lanes);
     };
     const bool clean = a.bases_clean && a.accum_clean;  // no identity row: the instantiation without the per-row test
-    if (a.accum_prefetch > 1) {
-      if (clean) accum_seg(AccumSegFn<FID, 2, true>{});
-      else accum_seg(AccumSegFn<FID, 2, false>{});
+    auto accum_pf = [&](auto pf, auto prio) {
+      if (clean) accum_seg(AccumSegFn<FID, decltype(pf)::value, true, decltype(prio)::value>{});
+      else accum_seg(AccumSegFn<FID, decltype(pf)::value, false, decltype(prio)::value>{});
+    };
+    using Pf1 = std::integral_constant<int, 1>;
+    using Pf2 = std::integral_constant<int, 2>;
+    if (a.accum_prio) {  // progress-keyed wave priority: the same arithmetic, scheduled differently on the device
+      if (a.accum_prefetch > 1) accum_pf(Pf2{}, std::true_type{});
+      else accum_pf(Pf1{}, std::true_type{});
     } else {
-      if (clean) accum_seg(AccumSegFn<FID, 1, true>{});
-      else accum_seg(AccumSegFn<FID, 1, false>{});
+      if (a.accum_prefetch > 1) accum_pf(Pf2{}, std::false_type{});
+      else accum_pf(Pf1{}, std::false_type{});
     }
     be.mark("fold");
     // big buckets (> 64 pieces) completely; then the heavy ones (> heavy_above) down to heavy_above positions; then

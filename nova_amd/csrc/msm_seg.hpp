@@ -107,7 +107,24 @@ struct SegPlan {
 
 // CLEAN: the key holds no identity point (MsmArgs::bases_clean; its window tables then hold none either), so the gathered row is
 // not tested for it -- 16 words OR-ed per addition otherwise.
-template <int FID, int PF = 1, bool CLEAN = false> struct AccumSegFn {
+//
+// PRIO: progress-keyed wave priority (device code only; option accum_prio).  The three waves of a SIMD come from three blocks and
+// differ in age; at equal priority the VALU arbiter serves the oldest first, so they drain one after the other and the youngest
+// runs the kernel's last stretch alone.  With PRIO a wave starts at priority 3 (plan step, search and prologue included) and
+// steps down to 2 / 1 / 0 when its trip index passes prio_sched's three thresholds (eighths of the segment length, 4 bits each
+// from the low end: 0x764 = half, three quarters, seven eighths): a wave that runs ahead crosses a threshold and yields.
+// s_setprio ignores EXEC, so everything that selects it is wave-uniform: the trip index is the same in every lane still in the
+// loop, and both it and the segment length go through readfirstlane.
+#if defined(NMX_ACCUM_TRACE)
+// Measuring build (scripts/accum_wave_trace.py), never the shipped one: lane 0 of every wave stores {block, wave of the block |
+// HW_ID << 8 | XCC_ID << 40, wall_clock64() at entry, wall_clock64() after its last flush} -- four 64-bit words per wave.
+struct AccumTrace {
+  uint64_t* buf;   // [words], null: no trace
+  uint64_t words;
+};
+#endif
+template <int FID, int PF = 1, bool CLEAN = false, bool PRIO = false> struct AccumSegFn {
+  static constexpr uint32_t kPrioSched = 0x764u;  // half, three quarters, seven eighths
   const AffineW* bases;
   const uint32_t* vals;
   const uint32_t* start;
@@ -117,6 +134,10 @@ template <int FID, int PF = 1, bool CLEAN = false> struct AccumSegFn {
   XYZZL* partial_raw;       // [lanes]
   uint32_t nbuckets, lanes, min_seg;
   SegPlan plan;  // the bucket lists of the passes after this kernel, written by its first lanes
+  uint32_t prio_sched = kPrioSched;  // PRIO: thresholds in eighths of the segment length (see above)
+#if defined(NMX_ACCUM_TRACE)
+  AccumTrace trace = {nullptr, 0};
+#endif
 
   // the smallest k >= k0 with end[k] > j (end[] is nondecreasing and end[nbuckets - 1] = total > j)
   NMX_HD uint32_t first_bucket_after(uint32_t k0, uint32_t j) const {
@@ -129,10 +150,42 @@ template <int FID, int PF = 1, bool CLEAN = false> struct AccumSegFn {
     return lo;
   }
   NMX_HD void operator()(uint32_t L) const {
+#if defined(NMX_ACCUM_TRACE) && defined(__HIP_DEVICE_COMPILE__)
+    const uint64_t t0 = wall_clock64();
+    run(L);
+    const uint64_t t1 = wall_clock64();  // the wave's lanes have reconverged: the last of them has flushed
+    const uint64_t w = (uint64_t)(L >> 6) * 4u;
+    if (trace.buf != nullptr && (threadIdx.x & 63u) == 0 && w + 4 <= trace.words) {
+      const uint64_t hw = __builtin_amdgcn_s_getreg((31 << 11) | 4), xcc = __builtin_amdgcn_s_getreg((31 << 11) | 20);
+      trace.buf[w] = blockIdx.x;
+      trace.buf[w + 1] = (threadIdx.x >> 6) | (hw << 8) | (xcc << 40);
+      trace.buf[w + 2] = t0;
+      trace.buf[w + 3] = t1;
+    }
+#else
+    run(L);
+#endif
+  }
+  NMX_HD void run(uint32_t L) const {
+#if defined(__HIP_DEVICE_COMPILE__)
+    if constexpr (PRIO) __builtin_amdgcn_s_setprio(3);
+#endif
     // plan first: lane L classifies buckets L, L + lanes, ... (the launch has whole waves: `lanes` is a multiple of 256)
     for (uint32_t kb = L & ~63u; kb < nbuckets; kb += lanes) plan(kb + (L & 63u), true);
     const uint32_t total = *total_p;
     const uint32_t seg = seg_len(total, lanes, min_seg);
+#if defined(__HIP_DEVICE_COMPILE__)
+    // PRIO: trip indices at which the wave steps down; seg >= 1, and a short segment (seg_min_len clamps to 8 or fewer) merely
+    // makes thresholds coincide -- the lowest priority among them wins, tested first in the loop
+    uint32_t p2_at = 0, p1_at = 0, p0_at = 0;
+    if constexpr (PRIO) {
+      const uint32_t useg = (uint32_t)__builtin_amdgcn_readfirstlane((int)seg);
+      const uint32_t sched = (uint32_t)__builtin_amdgcn_readfirstlane((int)prio_sched);
+      p2_at = (uint32_t)(((uint64_t)useg * (sched & 15u)) >> 3);
+      p1_at = (uint32_t)(((uint64_t)useg * ((sched >> 4) & 15u)) >> 3);
+      p0_at = (uint32_t)(((uint64_t)useg * ((sched >> 8) & 15u)) >> 3);
+    }
+#endif
     const uint64_t a64 = (uint64_t)L * seg;
     if (a64 >= total) return;
     const uint32_t a = (uint32_t)a64, b = (a64 + seg < total) ? a + seg : total;
@@ -151,6 +204,14 @@ template <int FID, int PF = 1, bool CLEAN = false> struct AccumSegFn {
     AffineW nx1 = cur;
     if (PF > 1 && a + 1 < b) nx1 = bases[vn & 0x7fffffffu];
     for (uint32_t j = a; j < b; j++) {
+#if defined(__HIP_DEVICE_COMPILE__)
+      if constexpr (PRIO) {  // every lane still in the loop is at the same trip: a scalar compare and branch per threshold
+        const uint32_t trip = (uint32_t)__builtin_amdgcn_readfirstlane((int)(j - a));
+        if (trip == p0_at) __builtin_amdgcn_s_setprio(0);
+        else if (trip == p1_at) __builtin_amdgcn_s_setprio(1);
+        else if (trip == p2_at) __builtin_amdgcn_s_setprio(2);
+      }
+#endif
       uint32_t vnn = vn, vnn2 = vn2;
       AffineW nxt = cur, nxt2 = nx1;
       if constexpr (PF == 1) {

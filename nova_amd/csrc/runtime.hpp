@@ -329,6 +329,7 @@ struct Global {
   std::atomic<uint32_t> no_quad_final{0};         // env NMX_TUNE_NO_QUAD_FINAL
   std::atomic<uint32_t> quad_final_below{65536};  // env NMX_TUNE_QUAD_FINAL_BELOW / option quad_final_below: the final pass runs four lanes per bucket below this many buckets
   std::atomic<uint32_t> accum_prefetch{0};        // env NMX_TUNE_ACCUM_PF / option accum_prefetch: 0 = by table size, 1, 2
+  std::atomic<uint32_t> accum_prio{0};            // env NMX_TUNE_ACCUM_PRIO / option accum_prio: progress-keyed wave priority in the segment accumulate (msm_seg.hpp AccumSegFn PRIO): 0 = by rule (accum_prio_sched), 1 = off, 2 = on (half / three quarters / seven eighths), 3 = on with equal quarters (A/B runs)
   std::atomic<uint32_t> horner_top{0};            // env NMX_TUNE_HORNER_TOP / option horner_top: suffix Horner from 1024 coefficients: 0 = single-pass scan (k_horner_scan); the two-pass kernels: 8 = 8-element chunks in registers, 4, 1 = chunk-per-lane recursion only
   std::atomic<uint32_t> eq_max_blocks{0};         // option eq_max_blocks: grid cap of the eq-factored sum passes (0 = 2048)
   std::atomic<uint32_t> horner_sub{0};            // option horner_sub: 512-coefficient sub-tiles per wave of the single-pass scan (0 = by size, 1, 2, 4)
@@ -367,8 +368,21 @@ struct Global {
   std::atomic<uint32_t> combine_mode{0};          // option combine: 0 = RCCL all-gather when the shards sit on >= 2 GPUs, host sum otherwise; 1 = host sum; 2 = RCCL required (also with one GPU: tests)
   std::atomic<uint32_t> cache_verify{0};          // option cache_verify: 0 = every hit re-hashes the caller's whole slice (on pool workers, under the MSM); 1 = rolling window (callers that register immutable keys)
   std::atomic<int32_t> launch_gap_ns{-1};         // cost of one dependent tiny launch on this box, measured once (capi.hip launch_gap_ns)
+#if defined(NMX_ACCUM_TRACE)
+  std::atomic<uint64_t*> accum_trace_buf{nullptr};  // measuring build: nmx_accum_trace_buffer (capi.hip)
+  std::atomic<uint64_t> accum_trace_words{0};
+#endif
 };
 extern Global& G;                // capi.hip (heap singleton, never destroyed)
+// option accum_prio -> the schedule word of the segment accumulate's progress-keyed priority (msm_seg.hpp AccumSegFn::prio_sched; 0: off).
+// By rule: on from 2^21 sorted entries (n x 16, the estimate seg_rounds() takes), where a lane's segment is longer than seg_min_len = 8.
+// Measured (profiles/accum_prio/rounds_sweep.txt, ms_per_step off -> on at one round of lanes): 2^17 pairs (segments of 11) 0.3348 ->
+// 0.3270 ms, 2^18 0.4888 -> 0.4751, 2^20 1.3386 -> 1.2872, 2^22 4.999 -> 4.807; 2^14 pairs (segments of 8: the thresholds sit one trip
+// apart) 0.1943 -> 0.1949, no gain, so off there.
+static inline uint32_t accum_prio_sched(size_t total_entries) {
+  const uint32_t v = G.accum_prio.load(std::memory_order_relaxed);
+  return v == 1 ? 0u : v == 2 ? 0x764u : v == 3 ? 0x642u : total_entries >= ((size_t)1 << 21) ? 0x764u : 0u;
+}
 void note_table_fallback();                // NMX_STAT_TABLE_FALLBACKS (capi.hip)
 void note_scan_timeout();                  // NMX_STAT_SCAN_TIMEOUTS
 int32_t launch_gap_ns(hipStream_t stream);  // measured once per process (capi.hip)
@@ -472,7 +486,18 @@ struct DeviceBackend {
   // wins by 4 % (0.687 against 0.719 ms); 2^21: two rounds by 1.6 % (2.986 against 3.036 at 1x, 2.987 at 3x).  Hence one
   // round up to 2^23 sorted entries (keys up to 2^19 points), two above.  Half rounds (1.5x) always lose: the second
   // round runs half empty (2^20: 1.704 ms).
-  static uint32_t seg_rounds(size_t total_entries) { return total_entries <= ((size_t)1 << 23) ? 1u : 2u; }
+  //
+  // With progress-keyed wave priority (AccumSegFn PRIO, option accum_prio) the extra rounds buy nothing up to 2^22 pairs: what they
+  // bought was a shorter drain -- at equal priority the oldest wave of a SIMD takes nearly every issue slot and finishes at 0.39 of the
+  // kernel, the second at 0.67, the youngest runs the last stretch alone (profiles/accum_prio/wave_finish_before.txt); a second round
+  // halves that stretch, priority keyed to progress shrinks it to the last eighth of a segment.  Sweep with priority on
+  // (profiles/accum_prio/rounds_sweep.txt; ms_per_step at 1x / 2x / 3x resident, ten alternating repetitions): 2^18 0.475 / 0.522 /
+  // 0.553, 2^20 1.287 / 1.322 / 1.329, 2^21 2.599 / 2.634 / 2.651, 2^22 4.807 / 4.857 / 4.839, 2^24 18.44 / 18.29 / 18.34 ms.  Hence
+  // with priority one round up to 2^26 estimated entries (keys up to 2^22 points; the fold keeps 3 pieces per bucket at c = 17), two
+  // above; without it the rule above.
+  static uint32_t seg_rounds(size_t total_entries, bool prio) {
+    return total_entries <= ((size_t)1 << (prio ? 26 : 23)) ? 1u : 2u;
+  }
   template <int FID> uint32_t seg_lanes(size_t total_entries) {
     static const uint32_t resident = [] {
       int blocks = 0, dev = 0;
@@ -482,7 +507,7 @@ struct DeviceBackend {
       return (uint32_t)blocks * 256u * (uint32_t)prop.multiProcessorCount;
     }();
     const uint32_t ov = G.seg_lanes_override.load(std::memory_order_relaxed);
-    return ov ? ov : seg_rounds(total_entries) * resident;
+    return ov ? ov : seg_rounds(total_entries, accum_prio_sched(total_entries) != 0) * resident;
   }
   template <int FID>
   void launch_fold_raw(const uint32_t* counters, const HeavyRec* list, XYZZL* partial_raw, uint32_t T, uint32_t cap,
