@@ -190,6 +190,38 @@ int nmx_bases_generate(int curve, uint64_t k0, size_t n, uint32_t flags, uint64_
 int nmx_bases_from_scalars(int curve, const void* base_xy64, const void* scalars, size_t n, uint32_t flags, uint64_t* handle);
 int nmx_bases_setup_from_tau(int curve, const void* tau32, size_t n, uint32_t flags, uint64_t* handle);
 
+/* ---- key derived by address -----------------------------------------------------------------------------
+ * CommitmentEngineTrait::ck_derive_by_address (src/traits/commitment.rs:177-194; Pedersen src/provider/pedersen.rs:360-381, HyperKZG
+ * src/provider/hyperkzg.rs:731-749): from a key ck and n addresses, a key of table_size points
+ *     derived[j] = sum of ck[i] over all i < n with addresses[i] == j,
+ * the identity where no address matches, so that Comm(L, ck) == Comm(T, derived) for L[i] = T[addresses[i]] (nmx_field_gather): a
+ * prover that looks things up commits to the small T instead of the n-sized L.  The reference adds serially on the host; here the
+ * key never leaves HBM: one window of a bucket MSM whose digit is the address -- pair sort, bucket bounds, over-long buckets split
+ * into tasks, accumulate, strided folds -- stopped before the bucket reduction, every bucket normalised to affine with one shared
+ * inversion per block of 256 (nova_amd/csrc/derive_key.hpp).  Skewed addresses (padding: a large share of all points on one index)
+ * are the normal case: no lane adds more than lmax points, by default min(4 x mean bucket, n / 2^14) within [32, 1024];
+ * nmx_set_option("derive_lmax", 2..1024) overrides it (0: the default; never changes a result).
+ *  - ck_handle: any registered key on ONE device; the points used are its first n (the reference's ck[i], i < addresses.len()).
+ *  - addresses: n 64-bit words (the reference's usize), a host pointer, or an HBM pointer with NMX_SCALARS_DEVICE.
+ *  - *handle: an ordinary key handle of table_size points that owns its memory (unregistering the source changes nothing), whole on
+ *    the device of its source: nmx_bases_read, nmx_msm_handle, nmx_commit, nmx_msm_batch_handle, nmx_msm_sparse_handle,
+ *    nmx_bases_unregister and a further nmx_bases_derive_by_address all work on it.
+ * flags: NMX_SCALARS_DEVICE (the addresses), NMX_BASES_PRECOMPUTE (window tables for the derived key, as for nmx_bases_generate).
+ * An index with no address, or one whose points cancel (P and -P), is stored as the all-zero x || y and the key then counts as holding
+ * identity points, exactly as nmx_bases_from_scalars marks a key with a zero scalar.  Identity SOURCE points (all-zero rows: a derived
+ * key, a key from zero scalars) contribute nothing; this is the one place the call is wider than the reference, which panics on such
+ * a key in ck_to_group_elements (pedersen.rs:346-358), and it is what makes a derivation from a derived key work.  n == 0 is allowed
+ * (the reference returns Ok): table_size identities.
+ * Errors, with nothing registered and *handle untouched: NMX_E_ARG for a NULL handle, NULL addresses with n > 0, table_size == 0,
+ * table_size >= 2^31 or n >= 2^31, a flag that does not apply, an address >= table_size (the reference's InvalidIndex: host addresses
+ * are checked on the host before a device is touched, HBM addresses by the kernel, which sends such an entry to the trash bucket and
+ * raises a flag -- no memory access depends on it, as in nmx_field_gather) and a source key sharded over several devices (out of
+ * scope: derive per shard on the caller's side, or register the source with sharding off); NMX_E_HANDLE for an unknown ck_handle and for
+ * n larger than the key (the reference's InvalidCommitmentKeyLength); NMX_E_TOO_LARGE when table_size plus the task count leaves 32
+ * bits; NMX_E_HIP when the workspace or the key does not fit.  Every check that needs no device precedes the first one that does. */
+int nmx_bases_derive_by_address(uint64_t ck_handle, const uint64_t* addresses, size_t n, size_t table_size,
+                                uint32_t flags, uint64_t* handle);
+
 /* ---- MSM ---------------------------------------------------------------------------------------------
  * DlogGroupExt::vartime_multiscalar_mul (src/provider/traits.rs:79; impls src/provider/bn256_grumpkin.rs:45-47,
  * src/provider/traits.rs:371-377) == msm() (src/provider/msm.rs:225-419):  out = sum_i scalars[i] * bases[i].
@@ -947,6 +979,8 @@ int nmx_set_window_bits(uint32_t c);
  * wave's loop over several tiles at tiny shapes; never changes a result),
  * "fixed_base_c" (window width of the table behind nmx_bases_from_scalars / nmx_bases_setup_from_tau: 4..16, default 8, other values:
  * NMX_E_ARG; the table holds ceil(BITS / c) x (2^c - 1) points of 64 bytes; never changes a result),
+ * "derive_lmax" (the longest run of points one lane of nmx_bases_derive_by_address adds before an index is split into tasks: 0 = by
+ * rule, else 2..1024, other values: NMX_E_ARG; tests reach the split and fold passes with few points; never changes a result),
  * "host_split" / "host_split_min_n" (an MSM with HOST scalars over at least host_split_min_n = 2^19 pairs of a key on one device is cut
  * into contiguous pieces (host_split = 255, the default: 2 / 3 / 4 pieces from 2^19 / 2^20 / 2^21 pairs; 2..16: that many) -- the
  * reference's own chunk + reduce decomposition, src/provider/msm.rs:564-574 -- so that piece i's scalars cross PCIe while piece

@@ -93,6 +93,17 @@ class CommitmentKey {
     check(nmx_bases_setup_from_tau(curve, tau.data(), k.n_, flags, &k.handle_));
     return k;
   }
+  // `ck_derive_by_address` (src/traits/commitment.rs:177-194; pedersen.rs:360-381, hyperkzg.rs:731-749), in HBM
+  // (nmx_bases_derive_by_address): derived[j] = sum of ck[i] over i < n with addresses[i] == j, the identity where nothing matches.
+  // addresses: host.  The result keeps this key's h and mont, as the reference keeps h.  InvalidIndex -> Error(NMX_E_ARG),
+  // InvalidCommitmentKeyLength -> Error(NMX_E_HANDLE).
+  CommitmentKey derive_by_address(const uint64_t* addresses, size_t n, size_t table_size, bool precompute = true) const {
+    return derive(addresses, n, table_size, precompute ? NMX_BASES_PRECOMPUTE : 0u);
+  }
+  // the same with `addresses` in HBM (nova::resident::derive_by_address)
+  CommitmentKey derive_by_device_address(const uint64_t* d_addresses, size_t n, size_t table_size, bool precompute = true) const {
+    return derive(d_addresses, n, table_size, NMX_SCALARS_DEVICE | (precompute ? NMX_BASES_PRECOMPUTE : 0u));
+  }
   CommitmentKey(CommitmentKey&& o) noexcept : curve_(o.curve_), n_(o.n_), h_(o.h_), mont_(o.mont_), handle_(o.handle_) {
     o.handle_ = 0;
   }
@@ -109,6 +120,12 @@ class CommitmentKey {
 
  private:
   CommitmentKey(int curve, size_t n, const Affine& h) : curve_(curve), n_(n), h_(h), mont_(false) {}
+  CommitmentKey derive(const uint64_t* addresses, size_t n, size_t table_size, uint32_t flags) const {
+    CommitmentKey k(curve_, table_size, h_);
+    k.mont_ = mont_;
+    check(nmx_bases_derive_by_address(handle_, addresses, n, table_size, flags, &k.handle_));
+    return k;
+  }
   static size_t next_power_of_two(size_t n) {
     size_t p = 1;
     while (p < n) p <<= 1;
@@ -467,6 +484,10 @@ inline Point commit(const CommitmentKey& ck, const void* v, size_t n, const Scal
   check(nmx_commit(ck.handle(), v, n, ck.h().data(), r.data(), kDev, p.xy.data(), &inf));
   p.is_inf = inf != 0;
   return p;
+}
+// CE::ck_derive_by_address (commitment.rs:177-194) with the n addresses (64-bit words) in HBM: the kernel checks them against table_size
+inline CommitmentKey derive_by_address(const CommitmentKey& ck, const uint64_t* d_addresses, size_t n, size_t table_size, bool precompute = true) {
+  return ck.derive_by_device_address(d_addresses, n, table_size, precompute);
 }
 inline uint64_t commit_begin(const CommitmentKey& ck, const void* v, size_t n, const Scalar& r) {  // one arm of a rayon::join of two commits
   uint64_t t = 0;

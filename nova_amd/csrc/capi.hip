@@ -1583,6 +1583,52 @@ int nmx_bases_setup_from_tau(int curve, const void* tau32, size_t n, uint32_t fl
   });
 }
 
+// ---- derivation by address (derive_key.hpp; src/traits/commitment.rs:177-194, pedersen.rs:360-381, hyperkzg.rs:731-749) ------------------
+// Every check that needs no device -- the host addresses among them, while they are narrowed to 32 bits -- precedes the lease; *handle is
+// written on success only.
+int nmx_bases_derive_by_address(uint64_t ck_handle, const uint64_t* addresses, size_t n, size_t table_size, uint32_t flags,
+                                uint64_t* handle) {
+  return guarded([&] {
+    require(handle != nullptr && (addresses != nullptr || n == 0), NMX_E_ARG, "null argument");
+    require(table_size >= 1 && table_size < (1ull << 31) && n < (1ull << 31), NMX_E_ARG,
+            "table_size must be at least 1, table_size and n below 2^31");
+    require((flags & ~(uint32_t)(NMX_SCALARS_DEVICE | NMX_BASES_PRECOMPUTE)) == 0, NMX_E_ARG,
+            "nmx_bases_derive_by_address: only NMX_SCALARS_DEVICE and NMX_BASES_PRECOMPUTE apply");
+    const bool dev = (flags & NMX_SCALARS_DEVICE) != 0;
+    std::vector<uint32_t> narrow;
+    if (!dev) {
+      narrow.resize(n);
+      for (size_t i = 0; i < n; i++) {
+        require(addresses[i] < table_size, NMX_E_ARG, "InvalidIndex: an address is not below table_size");
+        narrow[i] = (uint32_t)addresses[i];
+      }
+    }
+    auto src = lookup(ck_handle);
+    require(slice_ok(*src, 0, n), NMX_E_HANDLE, "InvalidCommitmentKeyLength: more addresses than key points");
+    require(src->parts.empty(), NMX_E_ARG, "nmx_bases_derive_by_address: the source key is sharded over several devices (not supported)");
+    DeriveCall dc;
+    dc.src = src.get();
+    dc.addr64 = dev ? addresses : nullptr;
+    dc.addr32 = dev ? nullptr : narrow.data();
+    dc.n = n;
+    dc.lmax = G.derive_lmax.load(std::memory_order_relaxed);
+    {
+      // lane counts are 32-bit: a lane per table index and per task (at most 2 (n / lmax + 1) tasks)
+      const uint32_t lmax = derive_shape((uint32_t)n, (uint32_t)table_size, dc.lmax).lmax;
+      require((uint64_t)table_size + 2 * ((uint64_t)n / lmax + 1) < 0xfff00000ull, NMX_E_TOO_LARGE, "table_size + tasks must be < 2^32");
+    }
+    const CurveOps& o = ops(src->curve);
+    CtxLease L(src->dev);  // the derived key lives where its source does, whole
+    struct Back {          // (the lease made that device current on this thread)
+      ~Back() { (void)hipSetDevice(G.device); }
+    } back;
+    *handle = publish(build_key(*L.c, src->curve, table_size, false, false, [&](Ctx& cx, BaseSet& part, size_t) {
+      part.dev = cx.dev;
+      o.derive(cx, part, dc, flags & NMX_BASES_PRECOMPUTE);
+    }));
+  });
+}
+
 int nmx_msm_handle(uint64_t handle, size_t offset, const void* scalars, size_t n, uint32_t flags,
                    uint8_t* out, uint8_t* out_is_inf) {
   return guarded([&] {
@@ -3569,6 +3615,11 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "fixed_base_c") {
       require(value >= kFbMinC && value <= kFbMaxC, NMX_E_ARG, "fixed_base_c: window width of the fixed-base key kernels, 4 .. 16");
       G.fixed_base_c = value;
+    }
+    else if (n == "derive_lmax") {
+      require(value == 0 || (value >= kDeriveLmaxMin && value <= kDeriveLmaxMax), NMX_E_ARG,
+              "derive_lmax: longest run one lane of nmx_bases_derive_by_address adds, 0 (default rule) or 2 .. 1024");
+      G.derive_lmax = value;
     }
     else if (n == "eq_max_blocks") G.eq_max_blocks = value;
     else if (n == "horner_spin_limit") G.horner_spin_limit = value;

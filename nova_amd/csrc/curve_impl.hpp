@@ -701,6 +701,44 @@ template <int CID> struct CurveImpl {
     }
     bs.d = d;
   }
+  // key[j] = sum of src[i], i < n, with address i == j (derive_key.hpp): a dry pass sizes the workspace, the second runs the chain; then
+  // the key's own window tables as `generate` builds them.  The flag word is read before anything is kept.
+  static void derive(Ctx& c, BaseSet& bs, const DeriveCall& dc, uint32_t flags) {
+    const size_t T = bs.n, n = dc.n;
+    void* d = nullptr;
+    table_shape<CID>(T, flags, &bs.pre_c, &bs.pre_W);
+    apply_table_limit(T, &bs.pre_c, &bs.pre_W);
+    HIPCHK(hipMalloc(&d, T * 64 * (bs.pre_W ? bs.pre_W : 1)));
+    try {
+      DeriveArgs a{};
+      a.bases = dc.src->d, a.out = (AffineW*)d;
+      a.n = (uint32_t)n, a.table_size = (uint32_t)T;
+      a.bases_clean = dc.src->any_identity ? 0u : 1u;
+      a.force_lmax = dc.lmax;
+      uint32_t hflags = 0;
+      for (int pass = 0; pass < 2; pass++) {
+        DeviceBackend be(c, pass == 0, false);
+        if (dc.addr64 || n == 0) {
+          a.addr64 = dc.addr64;
+        } else {
+          uint32_t* da = be.alloc<uint32_t>(n);
+          a.addr32 = da;
+          if (pass == 1) HIPCHK(hipMemcpyAsync(da, dc.addr32, n * 4, hipMemcpyHostToDevice, c.stream));
+        }
+        derive_pipeline<DeviceBackend, BF>(be, a, &hflags);
+        if (pass == 0) arena_reserve(c, be.used);
+      }
+      require(!(hflags & DK_ERR_ADDRESS), NMX_E_ARG, "InvalidIndex: an address is not below table_size");
+      build_tables<CID>(c, d, T, bs.pre_c, bs.pre_W);
+      HIPCHK(hipStreamSynchronize(c.stream));
+      bs.any_identity = (hflags & DK_ANY_IDENTITY) != 0;  // an empty index, or one whose points cancel
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);
+      (void)hipFree(d);
+      throw;
+    }
+    bs.d = d;
+  }
   static void internal_to_canonical(uint8_t* e, size_t count) {
     for (size_t i = 0; i < count; i++) {
       Fp<BF> f = fp_from_bytes<BF>(e + 32 * i);
@@ -734,7 +772,7 @@ template <int CID> struct CurveImpl {
   }
   static CurveOps ops() {
     return CurveOps{&msm_key, &msm_key_batch, &batch_limit, &commit, &upload, &check_point_host, FpParams<BF>::PW,
-                    &generate, &fixed_base, &internal_to_canonical, &point_sum, &blind_term, &check_layout, &table_bytes, &commit_batch, SF};
+                    &generate, &fixed_base, &derive, &internal_to_canonical, &point_sum, &blind_term, &check_layout, &table_bytes, &commit_batch, SF};
   }
 };
 

@@ -28,6 +28,7 @@
 #include "msm_pipeline.hpp"
 #include "curve_quad.hpp"
 #include "fixed_base.hpp"
+#include "derive_key.hpp"
 #include "host_point4.hpp"
 
 namespace nmx {
@@ -337,6 +338,7 @@ struct Global {
   std::atomic<uint32_t> horner_window{64};        // option horner_window: tiles per look-back round of the single-pass scan (tests: 1 .. 63 force the multi-round path)
   std::atomic<uint32_t> mercury_seg_rows{0};      // option mercury_seg_rows: rows per segment of Mercury's division kernels (mercury.hpp mercury_plan; 0 = by size; tests force the multi-segment path at tiny shapes)
   std::atomic<uint32_t> fixed_base_c{kFbDefaultC};         // option fixed_base_c: window width of the fixed-base key kernels (fixed_base.hpp; 4 .. 16, default 8: docs/measurements.md)
+  std::atomic<uint32_t> derive_lmax{0};            // option derive_lmax: the longest run one lane of nmx_bases_derive_by_address adds (derive_key.hpp; 0 = derive_default_lmax, 2 .. 1024; tests reach the split and fold passes with few points)
   std::atomic<uint32_t> neutron_max_blocks{0};    // option neutron_max_blocks: the largest grid of the two NeutronNova sums (neutron.hpp neutron_blocks; 0 = by size; tests force a wave's loop over tiles at tiny shapes)
   std::atomic<uint32_t> seg_heavy_above{0};       // env NMX_TUNE_SEG_HEAVY_ABOVE / option seg_heavy_above: 0 = by pieces per bucket (8 or 12)
   std::atomic<uint32_t> prefix_tables{2};         // env NMX_TUNE_PREFIX_TABLES / option prefix_tables: narrower table sets over a key's first points (capi.hip add_prefix_tables): 0 none, 1 the 2^18-point set of wide-table keys only, 2 the whole chain (batches descend it)
@@ -812,6 +814,15 @@ struct FixedBaseCall {
   uint32_t c = 8;                      // window width, 4 .. 16
 };
 
+// one derivation by address (derive_key.hpp): bs.n = table_size rows from the first n points of `src` (single-device, on bs's device)
+struct DeriveCall {
+  const BaseSet* src = nullptr;
+  const uint64_t* addr64 = nullptr;  // HBM, n words: checked by the kernel
+  const uint32_t* addr32 = nullptr;  // host, n words narrowed and checked by the caller (when addr64 is null)
+  size_t n = 0;
+  uint32_t lmax = 0;                 // option derive_lmax
+};
+
 struct CurveOps {
   // out = sum scalars[i] * key[offset + i], i < n, through the key's window tables when it has them
   void (*msm_key)(Ctx&, const BaseSet&, size_t offset, size_t n, const MsmCall&, uint32_t flags, uint8_t* out,
@@ -834,6 +845,9 @@ struct CurveOps {
   // fill bs as `generate` does, with bs.n fixed-base multiples; flags: NMX_BASES_PRECOMPUTE.  NMX_E_SCALAR_RANGE (nothing kept) when a
   // device scalar is not below r
   void (*fixed_base)(Ctx&, BaseSet& bs, const FixedBaseCall&, uint32_t flags);
+  // fill bs as `generate` does, with bs.n sums of the source's points by address; flags: NMX_BASES_PRECOMPUTE.  NMX_E_ARG (nothing kept)
+  // when a device address is not below bs.n
+  void (*derive)(Ctx&, BaseSet& bs, const DeriveCall&, uint32_t flags);
   void (*internal_to_canonical)(uint8_t* elems32, size_t count);  // host, in place
   // host: sum of 128-byte partials -> affine point, or (flags & NMX_OUT_PARTIAL) one more partial
   void (*point_sum)(const uint8_t* partials128, size_t count, uint32_t flags, uint8_t* out, uint8_t* inf);

@@ -259,6 +259,18 @@ class CommitmentKey:
         _check(L.lib().nmx_bases_setup_from_tau(curve, t.ctypes.data, num, flags, ctypes.byref(h)))
         return cls(curve, h.value, num, h_xy64 if h_xy64 is not None else bytes(64), mont)
 
+    def derive_by_address(self, addresses, table_size, precompute=True):
+        """`ck_derive_by_address` (src/traits/commitment.rs:177-194; pedersen.rs:360-381, hyperkzg.rs:731-749), in HBM
+        (nmx_bases_derive_by_address): a key of table_size points, derived[j] = sum of self[i] over i < len(addresses) with
+        addresses[i] == j, the identity where nothing matches -- so commit(self, L) == commit(derived, T) for L[i] = T[addresses[i]].
+        addresses: a sequence or numpy uint64 array on the host, or a CUDA tensor of uint64 (used in place).  The result keeps this key's
+        h and mont, as the reference keeps h."""
+        ap, n, dev, _keep = _scalar_arg(addresses, 8)
+        h = ctypes.c_uint64(0)
+        flags = dev | (L.BASES_PRECOMPUTE if precompute else 0)
+        _check(L.lib().nmx_bases_derive_by_address(self.handle, ap, n, int(table_size), flags, ctypes.byref(h)))
+        return CommitmentKey(self.curve, h.value, int(table_size), self.h, self.mont)
+
     def shard_plan(self, offset=0, n=None):
         """[(device, offset inside the shard, count)] for a call over key[offset, offset + n), from the layout the
         REGISTERED key has (nmx_bases_shard_plan) -- the plan to cut shard-resident scalar pieces by.  (A generated key is
@@ -416,6 +428,10 @@ class CommitmentEngine:
     def setup_from_tau(self, n, tau, h_xy64=None, mont=False, precompute=True):
         """`CommitmentEngine::setup` with tau known (src/provider/hyperkzg.rs:565-567 -> :357-410): see CommitmentKey.setup_from_tau"""
         return CommitmentKey.setup_from_tau(self.group.curve, n, tau, h_xy64, mont, precompute)
+
+    def ck_derive_by_address(self, ck, addresses, table_size, precompute=True):
+        """`ck_derive_by_address` (src/traits/commitment.rs:177-194): see CommitmentKey.derive_by_address"""
+        return ck.derive_by_address(addresses, table_size, precompute)
 
     def commit(self, ck, v, r=None, mont=False, partial=False):
         """msm(v, ck[..len v]) + h*r  (pedersen.rs:263-270, hyperkzg.rs:584-591).  v may be a ShardedVector."""
