@@ -222,6 +222,45 @@ int nmx_bases_setup_from_tau(int curve, const void* tau32, size_t n, uint32_t fl
 int nmx_bases_derive_by_address(uint64_t ck_handle, const uint64_t* addresses, size_t n, size_t table_size,
                                 uint32_t flags, uint64_t* handle);
 
+/* ---- key algebra ----------------------------------------------------------------------------------------
+ * CommitmentKeyExtTrait (src/provider/pedersen.rs:430-529): split_at, combine, fold, scale and reinterpret_commitments_as_ck, the
+ * divide-and-conquer interface the reference's inner-product argument is written against (src/provider/ipa_pc.rs:183,194,212-227,255,
+ * 294,310,353-363,380), on keys that stay in HBM (nova_amd/csrc/key_ext.hpp).  nmx_ipa_prove / nmx_ipa_verify never fold the key and do
+ * not need these; a caller that wants the folded or scaled key itself does.
+ *  - nmx_bases_concat: the new key is the concatenation of rows [offsets[j], offsets[j] + lens[j]) of ck_handles[j], j < k, 1 <= k <= 8.
+ *    offsets == NULL: all zero.  lens == NULL: every key whole (from its offset to its end).  split_at(n) is two calls with k = 1;
+ *    combine is k = 2; ipa_pc.rs's ck_R.combine(&ck_c) is ONE call with the ranges (ck, n/2, n/2) and (ck_c, 0, 1).  The copies are device
+ *    to device in the internal form; no point arithmetic is done.  The result counts as holding identity points if ANY source key
+ *    does, whether or not the copied rows hold one: conservative (an MSM over it then reads the rows to skip identities), never wrong.
+ *  - nmx_bases_fold: fold(w1, w2) (pedersen.rs:484-497): with h = n / 2, out[i] = w1 * ck[offset + i] + w2 * ck[offset + h + i], i < h.
+ *    For odd n the last point is ignored, as in the reference (self.ck.len() / 2 both times).
+ *  - nmx_bases_scale: scale(r) (pedersen.rs:500-512): out[i] = r * ck[offset + i], i < n.
+ *  - reinterpret_commitments_as_ck (pedersen.rs:515-528) needs no call of its own: it is nmx_bases_register over the commitments' x || y.
+ * w1, w2 and r are 32-byte HOST values (transcript challenges; there is no HBM form), canonical, or Montgomery words with
+ * NMX_SCALARS_MONT.  The host recodes them once into a signed-binary digit stream (the non-adjacent form of r; Solinas' joint sparse form
+ * of (w1, w2)) that the kernel arguments carry: one lane per output point, every lane on the same digits, doublings and mixed additions
+ * only, one shared inversion per block of 256 on the way to the affine rows.
+ * flags: NMX_SCALARS_MONT (fold and scale only), NMX_BASES_PRECOMPUTE (window tables for the result, as for nmx_bases_generate; a folded
+ * key that is used for two MSMs and folded again does not want them).  Every other flag, NMX_ASYNC included: NMX_E_ARG.
+ * *handle: an ordinary key handle that owns its memory (unregistering a source changes nothing), whole on the device of its source:
+ * nmx_bases_read, nmx_msm_handle, nmx_commit, nmx_msm_batch_handle, nmx_msm_sparse_handle, nmx_bases_derive_by_address,
+ * nmx_bases_unregister and a further concat, fold or scale all work on it.  An identity SOURCE row (all zero) contributes nothing, as the
+ * reference's msm skips it (msm.rs:247-249).  An output that is the identity -- a zero weight, w1 L = -w2 R, an identity row under scale --
+ * is stored as the all-zero x || y and the key then counts as holding identity points, exactly as nmx_bases_from_scalars marks a key with
+ * a zero scalar.
+ * Errors, with nothing registered and *handle untouched: NMX_E_ARG for a NULL handle, a NULL handles array or a NULL weight; k == 0 or
+ * k > 8; a zero total length (concat), n == 0 (scale), n < 2 (fold); any length or total >= 2^31; a flag that does not apply; concat
+ * sources of different curves or on different devices; a source key sharded over several devices (out of scope, as for
+ * nmx_bases_derive_by_address).  NMX_E_SCALAR_RANGE for a weight whose stored words are >= r, checked on the host (the modulus is the
+ * key's, so an unknown handle is reported first).  NMX_E_HANDLE for an unknown handle and for a range that leaves its key.  NMX_E_HIP when
+ * the key does not fit.  Every check that needs no device precedes the first one that does. */
+int nmx_bases_concat(const uint64_t* ck_handles, const size_t* offsets, const size_t* lens, size_t k,
+                     uint32_t flags, uint64_t* handle);
+int nmx_bases_fold(uint64_t ck_handle, size_t offset, size_t n, const void* w1, const void* w2,
+                   uint32_t flags, uint64_t* handle);
+int nmx_bases_scale(uint64_t ck_handle, size_t offset, size_t n, const void* r,
+                    uint32_t flags, uint64_t* handle);
+
 /* ---- MSM ---------------------------------------------------------------------------------------------
  * DlogGroupExt::vartime_multiscalar_mul (src/provider/traits.rs:79; impls src/provider/bn256_grumpkin.rs:45-47,
  * src/provider/traits.rs:371-377) == msm() (src/provider/msm.rs:225-419):  out = sum_i scalars[i] * bases[i].

@@ -10,6 +10,7 @@
 #include <cstdint>
 #include <stdexcept>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "nova_mi355x.h"
@@ -103,6 +104,51 @@ class CommitmentKey {
   // the same with `addresses` in HBM (nova::resident::derive_by_address)
   CommitmentKey derive_by_device_address(const uint64_t* d_addresses, size_t n, size_t table_size, bool precompute = true) const {
     return derive(d_addresses, n, table_size, NMX_SCALARS_DEVICE | (precompute ? NMX_BASES_PRECOMPUTE : 0u));
+  }
+  // `CommitmentKeyExtTrait` (src/provider/pedersen.rs:430-529), in HBM (nmx_bases_concat / _fold / _scale).  Every result keeps this key's
+  // h and mont, as the reference keeps h; the default is NO window tables: a folded key is used for two MSMs and folded again.
+  // (reinterpret_commitments_as_ck, pedersen.rs:515-528, is the registering constructor over the commitments' coordinates.)
+  struct Part {  // rows [offset, offset + len) of *key
+    const CommitmentKey* key;
+    size_t offset, len;
+  };
+  // the rows of 1 to 8 parts, copied device to device; h and mont come from this key, which need not be among the parts
+  CommitmentKey concat(const std::vector<Part>& parts, bool precompute = false) const {
+    std::vector<uint64_t> hs;
+    std::vector<size_t> offs, lens;
+    size_t total = 0;
+    for (const Part& p : parts) {
+      hs.push_back(p.key->handle_), offs.push_back(p.offset), lens.push_back(p.len);
+      total += p.len;
+    }
+    CommitmentKey k(curve_, total, h_);
+    k.mont_ = mont_;
+    check(nmx_bases_concat(hs.data(), offs.data(), lens.data(), parts.size(), precompute ? NMX_BASES_PRECOMPUTE : 0u, &k.handle_));
+    return k;
+  }
+  // `split_at` (pedersen.rs:461-472): (ck[..n], ck[n..]), two keys of their own
+  std::pair<CommitmentKey, CommitmentKey> split_at(size_t n) const {
+    if (n > n_) throw Error(NMX_E_HANDLE, "split_at: n beyond the key");
+    return {concat({Part{this, 0, n}}), concat({Part{this, n, n_ - n}})};
+  }
+  // `combine` (pedersen.rs:474-481): this key's points, then other's
+  CommitmentKey combine(const CommitmentKey& other) const { return concat({Part{this, 0, n_}, Part{&other, 0, other.n_}}); }
+  // `fold` (pedersen.rs:484-497): with h = len() / 2, out[i] = w1 * ck[i] + w2 * ck[h + i]; for an odd length the last point is ignored.
+  // mont names the form of w1 and w2.
+  CommitmentKey fold(const Scalar& w1, const Scalar& w2, bool mont = false, bool precompute = false) const {
+    CommitmentKey k(curve_, n_ / 2, h_);
+    k.mont_ = mont_;
+    const uint32_t flags = (mont ? NMX_SCALARS_MONT : 0u) | (precompute ? NMX_BASES_PRECOMPUTE : 0u);
+    check(nmx_bases_fold(handle_, 0, n_, w1.data(), w2.data(), flags, &k.handle_));
+    return k;
+  }
+  // `scale` (pedersen.rs:500-512): out[i] = r * ck[i].  mont names the form of r.
+  CommitmentKey scale(const Scalar& r, bool mont = false, bool precompute = false) const {
+    CommitmentKey k(curve_, n_, h_);
+    k.mont_ = mont_;
+    const uint32_t flags = (mont ? NMX_SCALARS_MONT : 0u) | (precompute ? NMX_BASES_PRECOMPUTE : 0u);
+    check(nmx_bases_scale(handle_, 0, n_, r.data(), flags, &k.handle_));
+    return k;
   }
   CommitmentKey(CommitmentKey&& o) noexcept : curve_(o.curve_), n_(o.n_), h_(o.h_), mont_(o.mont_), handle_(o.handle_) {
     o.handle_ = 0;

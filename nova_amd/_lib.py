@@ -71,6 +71,9 @@ def lib():
     L.nmx_bases_from_scalars.argtypes = [i, vp, vp, sz, u32, ctypes.POINTER(u64)]
     L.nmx_bases_setup_from_tau.argtypes = [i, vp, sz, u32, ctypes.POINTER(u64)]
     L.nmx_bases_derive_by_address.argtypes = [u64, vp, sz, sz, u32, ctypes.POINTER(u64)]
+    L.nmx_bases_concat.argtypes = [ctypes.POINTER(u64), ctypes.POINTER(sz), ctypes.POINTER(sz), sz, u32, ctypes.POINTER(u64)]
+    L.nmx_bases_fold.argtypes = [u64, sz, sz, vp, vp, u32, ctypes.POINTER(u64)]
+    L.nmx_bases_scale.argtypes = [u64, sz, sz, vp, u32, ctypes.POINTER(u64)]
     L.nmx_bases_register_ptau.argtypes = [i, ctypes.c_char_p, sz, sz, u32, ctypes.POINTER(u64)]
     L.nmx_bases_register_keyfile.argtypes = [i, ctypes.c_char_p, sz, u32, ctypes.POINTER(u64), vp]
     L.nmx_msm.argtypes = [i, vp, vp, sz, u32, vp, vp]

@@ -1629,6 +1629,105 @@ int nmx_bases_derive_by_address(uint64_t ck_handle, const uint64_t* addresses, s
   });
 }
 
+// ---- key algebra (key_ext.hpp; CommitmentKeyExtTrait, src/provider/pedersen.rs:430-529) ---------------------------------------------------
+// Every check that needs no device precedes the lease; *handle is written on success only.  The weights' range is known once the key (and
+// with it the curve) is: an unknown handle is therefore reported before a weight that is out of range.
+static void require_single_device(const BaseSet& bs, const char* what) {
+  require(bs.parts.empty(), NMX_E_ARG, what);
+}
+int nmx_bases_concat(const uint64_t* ck_handles, const size_t* offsets, const size_t* lens, size_t k, uint32_t flags, uint64_t* handle) {
+  return guarded([&] {
+    require(handle != nullptr && ck_handles != nullptr, NMX_E_ARG, "null argument");
+    require(k >= 1 && k <= 8, NMX_E_ARG, "nmx_bases_concat: between 1 and 8 ranges");
+    if (lens) {
+      size_t total = 0;
+      for (size_t j = 0; j < k; j++) {
+        require(lens[j] < (1ull << 31), NMX_E_ARG, "nmx_bases_concat: a length is not below 2^31");
+        total += lens[j];
+      }
+      require(total >= 1 && total < (1ull << 31), NMX_E_ARG, "nmx_bases_concat: the total length must be at least 1 and below 2^31");
+    }
+    require((flags & ~(uint32_t)NMX_BASES_PRECOMPUTE) == 0, NMX_E_ARG, "nmx_bases_concat: only NMX_BASES_PRECOMPUTE applies");
+    BaseRef src[8];
+    for (size_t j = 0; j < k; j++) src[j] = lookup(ck_handles[j]);
+    size_t off[8], len[8], total = 0;
+    bool any_identity = false;
+    for (size_t j = 0; j < k; j++) {
+      require(src[j]->curve == src[0]->curve, NMX_E_ARG, "nmx_bases_concat: the source keys are of different curves");
+      require_single_device(*src[j], "nmx_bases_concat: a source key is sharded over several devices (not supported)");
+      require(src[j]->dev == src[0]->dev, NMX_E_ARG, "nmx_bases_concat: the source keys are on different devices");
+      off[j] = offsets ? offsets[j] : 0;
+      require(off[j] <= src[j]->n, NMX_E_HANDLE, "nmx_bases_concat: a range leaves its key");
+      len[j] = lens ? lens[j] : src[j]->n - off[j];
+      require(slice_ok(*src[j], off[j], len[j]), NMX_E_HANDLE, "nmx_bases_concat: a range leaves its key");
+      total += len[j];  // (no wrap: every key holds fewer than 2^31 points)
+      any_identity |= src[j]->any_identity;
+    }
+    require(total >= 1 && total < (1ull << 31), NMX_E_ARG, "nmx_bases_concat: the total length must be at least 1 and below 2^31");
+    const int curve = src[0]->curve;
+    const CurveOps& o = ops(curve);
+    CtxLease L(src[0]->dev);  // the new key lives where its sources do, whole
+    struct Back {
+      ~Back() { (void)hipSetDevice(G.device); }
+    } back;
+    *handle = publish(build_key(*L.c, curve, total, false, false, [&](Ctx& cx, BaseSet& part, size_t) {
+      part.dev = cx.dev;
+      const BaseFill fill = [&](void* d, hipStream_t stream) {  // device to device, in the internal form
+        size_t at = 0;
+        for (size_t j = 0; j < k; j++) {
+          if (len[j])
+            HIPCHK(hipMemcpyAsync((char*)d + at * 64, (const char*)src[j]->d + off[j] * 64, len[j] * 64, hipMemcpyDeviceToDevice, stream));
+          at += len[j];
+        }
+      };
+      o.upload(cx, part, nullptr, NMX_BASES_DEVICE | NMX_BASES_INTERNAL | (flags & NMX_BASES_PRECOMPUTE), &fill);
+      part.any_identity = any_identity;  // conservative: the copied rows may hold none
+    }));
+  });
+}
+// the body of fold (w2 != nullptr) and scale
+static void key_lincomb_call(uint64_t ck_handle, size_t offset, size_t n, const void* w1, const void* w2, bool fold, uint32_t flags,
+                             uint64_t* handle) {
+  require(handle != nullptr && w1 != nullptr && (!fold || w2 != nullptr), NMX_E_ARG, "null argument");
+  require(n >= (fold ? 2u : 1u) && n < (1ull << 31), NMX_E_ARG,
+          fold ? "nmx_bases_fold: n must be at least 2 and below 2^31" : "nmx_bases_scale: n must be at least 1 and below 2^31");
+  require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_BASES_PRECOMPUTE)) == 0, NMX_E_ARG,
+          "nmx_bases_fold / nmx_bases_scale: only NMX_SCALARS_MONT and NMX_BASES_PRECOMPUTE apply");
+  auto src = lookup(ck_handle);
+  const CurveOps& o = ops(src->curve);
+  KeyExtCall kc;
+  {
+    uint32_t w[2][8] = {};
+    memcpy(w[0], w1, 32);
+    if (fold) memcpy(w[1], w2, 32);
+    require_canonical(o.scalar_field, w, fold ? 2 : 1, "a weight is not below the scalar field's modulus");
+    if (flags & NMX_SCALARS_MONT)
+      with_field(o.scalar_field, [&](auto F) {
+        for (int i = 0; i < 2; i++) Fp<decltype(F)::value>::from_words(w[i]).mont256_to_canonical().to_words(w[i]);
+      });
+    require(ke_recode(w[0], fold ? w[1] : nullptr, &kc.dig), NMX_E_TOO_LARGE, "key_ext: digit stream too long");  // (not reached: the weights are below r < 2^255)
+  }
+  require(slice_ok(*src, offset, n), NMX_E_HANDLE, "offset + n beyond the registered key");
+  require_single_device(*src, "nmx_bases_fold / nmx_bases_scale: the source key is sharded over several devices (not supported)");
+  const size_t m = fold ? n / 2 : n;  // an odd n: the last point is ignored (pedersen.rs:486)
+  kc.src = src.get();
+  kc.off0 = offset, kc.off1 = offset + m, kc.k = fold ? 2u : 1u;
+  CtxLease L(src->dev);  // the new key lives where its source does, whole
+  struct Back {
+    ~Back() { (void)hipSetDevice(G.device); }
+  } back;
+  *handle = publish(build_key(*L.c, src->curve, m, false, false, [&](Ctx& cx, BaseSet& part, size_t) {
+    part.dev = cx.dev;
+    o.key_lincomb(cx, part, kc, flags & NMX_BASES_PRECOMPUTE);
+  }));
+}
+int nmx_bases_fold(uint64_t ck_handle, size_t offset, size_t n, const void* w1, const void* w2, uint32_t flags, uint64_t* handle) {
+  return guarded([&] { key_lincomb_call(ck_handle, offset, n, w1, w2, true, flags, handle); });
+}
+int nmx_bases_scale(uint64_t ck_handle, size_t offset, size_t n, const void* r, uint32_t flags, uint64_t* handle) {
+  return guarded([&] { key_lincomb_call(ck_handle, offset, n, r, nullptr, false, flags, handle); });
+}
+
 int nmx_msm_handle(uint64_t handle, size_t offset, const void* scalars, size_t n, uint32_t flags,
                    uint8_t* out, uint8_t* out_is_inf) {
   return guarded([&] {

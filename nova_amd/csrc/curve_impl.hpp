@@ -739,6 +739,36 @@ template <int CID> struct CurveImpl {
     }
     bs.d = d;
   }
+  // key[i] = w1 * src[off0 + i] (+ w2 * src[off1 + i]) (key_ext.hpp): one launch, then the key's own window tables as `generate` builds
+  // them.  The flag word is read before anything is kept.
+  static void key_lincomb(Ctx& c, BaseSet& bs, const KeyExtCall& kc, uint32_t flags) {
+    const size_t m = bs.n;
+    void* d = nullptr;
+    table_shape<CID>(m, flags, &bs.pre_c, &bs.pre_W);
+    apply_table_limit(m, &bs.pre_c, &bs.pre_W);
+    HIPCHK(hipMalloc(&d, m * 64 * (bs.pre_W ? bs.pre_W : 1)));
+    try {
+      arena_reserve(c, 256);
+      DeviceBackend be(c, false, false);
+      uint32_t* dflags = be.alloc<uint32_t>(64);
+      HIPCHK(hipMemsetAsync(dflags, 0, 8, c.stream));
+      KeLincombArgs a{};
+      a.p0 = (const AffineW*)kc.src->d + kc.off0, a.p1 = (const AffineW*)kc.src->d + kc.off1;
+      a.out = (AffineW*)d, a.flags = dflags;
+      a.m = (uint32_t)m, a.k = kc.k, a.dig = kc.dig;
+      be.launch_kernel(k_key_lincomb<BF>, (uint32_t)((m + kFbThreads - 1) / kFbThreads), kFbThreads, a);
+      uint32_t hflags = 0;
+      HIPCHK(hipMemcpyAsync(&hflags, dflags, 4, hipMemcpyDeviceToHost, c.stream));
+      build_tables<CID>(c, d, m, bs.pre_c, bs.pre_W);
+      HIPCHK(hipStreamSynchronize(c.stream));
+      bs.any_identity = (hflags & FB_ANY_IDENTITY) != 0;  // a zero weight, w1 L = -w2 R, identity source rows
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);
+      (void)hipFree(d);
+      throw;
+    }
+    bs.d = d;
+  }
   static void internal_to_canonical(uint8_t* e, size_t count) {
     for (size_t i = 0; i < count; i++) {
       Fp<BF> f = fp_from_bytes<BF>(e + 32 * i);
@@ -772,7 +802,7 @@ template <int CID> struct CurveImpl {
   }
   static CurveOps ops() {
     return CurveOps{&msm_key, &msm_key_batch, &batch_limit, &commit, &upload, &check_point_host, FpParams<BF>::PW,
-                    &generate, &fixed_base, &derive, &internal_to_canonical, &point_sum, &blind_term, &check_layout, &table_bytes, &commit_batch, SF};
+                    &generate, &fixed_base, &derive, &key_lincomb, &internal_to_canonical, &point_sum, &blind_term, &check_layout, &table_bytes, &commit_batch, SF};
   }
 };
 

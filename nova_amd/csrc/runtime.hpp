@@ -29,6 +29,7 @@
 #include "curve_quad.hpp"
 #include "fixed_base.hpp"
 #include "derive_key.hpp"
+#include "key_ext.hpp"
 #include "host_point4.hpp"
 
 namespace nmx {
@@ -823,6 +824,14 @@ struct DeriveCall {
   uint32_t lmax = 0;                 // option derive_lmax
 };
 
+// one fold or scale (key_ext.hpp): bs.n rows out[i] = w1 * src[off0 + i] (+ w2 * src[off1 + i]) (single-device source, on bs's device)
+struct KeyExtCall {
+  const BaseSet* src = nullptr;
+  size_t off0 = 0, off1 = 0;
+  uint32_t k = 1;        // 1: scale, 2: fold
+  KeDigits dig;          // ke_recode of the canonical weights
+};
+
 struct CurveOps {
   // out = sum scalars[i] * key[offset + i], i < n, through the key's window tables when it has them
   void (*msm_key)(Ctx&, const BaseSet&, size_t offset, size_t n, const MsmCall&, uint32_t flags, uint8_t* out,
@@ -848,6 +857,8 @@ struct CurveOps {
   // fill bs as `generate` does, with bs.n sums of the source's points by address; flags: NMX_BASES_PRECOMPUTE.  NMX_E_ARG (nothing kept)
   // when a device address is not below bs.n
   void (*derive)(Ctx&, BaseSet& bs, const DeriveCall&, uint32_t flags);
+  // fill bs as `generate` does, with bs.n shared-weight combinations of the source's rows; flags: NMX_BASES_PRECOMPUTE
+  void (*key_lincomb)(Ctx&, BaseSet& bs, const KeyExtCall&, uint32_t flags);
   void (*internal_to_canonical)(uint8_t* elems32, size_t count);  // host, in place
   // host: sum of 128-byte partials -> affine point, or (flags & NMX_OUT_PARTIAL) one more partial
   void (*point_sum)(const uint8_t* partials128, size_t count, uint32_t flags, uint8_t* out, uint8_t* inf);

@@ -271,6 +271,48 @@ class CommitmentKey:
         _check(L.lib().nmx_bases_derive_by_address(self.handle, ap, n, int(table_size), flags, ctypes.byref(h)))
         return CommitmentKey(self.curve, h.value, int(table_size), self.h, self.mont)
 
+    # ---- CommitmentKeyExtTrait (src/provider/pedersen.rs:430-529), in HBM.  Every result keeps this key's h and mont, as the reference
+    # keeps h; the default is NO window tables: a folded key is used for two MSMs and folded again.
+    # (reinterpret_commitments_as_ck, pedersen.rs:515-528, is CommitmentKey.from_host over the commitments' x || y.)
+    def concat(self, parts, precompute=False):
+        """The key made of the rows [offset, offset + len) of every (key, offset, len) in `parts` (1 to 8 of them), copied device to
+        device (nmx_bases_concat).  h and mont come from self, which need not be among the parts."""
+        parts = [(k, int(o), int(m)) for k, o, m in parts]
+        hs = (ctypes.c_uint64 * len(parts))(*[k.handle for k, _o, _m in parts])
+        offs = (ctypes.c_size_t * len(parts))(*[o for _k, o, _m in parts])
+        lens = (ctypes.c_size_t * len(parts))(*[m for _k, _o, m in parts])
+        h = ctypes.c_uint64(0)
+        _check(L.lib().nmx_bases_concat(hs, offs, lens, len(parts), L.BASES_PRECOMPUTE if precompute else 0, ctypes.byref(h)))
+        return CommitmentKey(self.curve, h.value, sum(m for _k, _o, m in parts), self.h, self.mont)
+
+    def split_at(self, n):
+        """`split_at` (pedersen.rs:461-472): (self[..n], self[n..]), two keys of their own"""
+        return self.concat([(self, 0, n)]), self.concat([(self, n, self.n - n)])
+
+    def combine(self, other):
+        """`combine` (pedersen.rs:474-481): self's points, then other's"""
+        return self.concat([(self, 0, self.n), (other, 0, other.n)])
+
+    def fold(self, w1, w2, mont=False, precompute=False):
+        """`fold` (pedersen.rs:484-497): with h = len(self) // 2, out[i] = w1 * self[i] + w2 * self[h + i] (nmx_bases_fold); for an odd
+        length the last point is ignored.  w1, w2: 32 bytes each on the host, canonical, or Montgomery words with mont."""
+        a, b = _host_u8(w1, 32), _host_u8(w2, 32)
+        assert a.size == 32 and b.size == 32, "a weight is one scalar"
+        h = ctypes.c_uint64(0)
+        flags = (L.SCALARS_MONT if mont else 0) | (L.BASES_PRECOMPUTE if precompute else 0)
+        _check(L.lib().nmx_bases_fold(self.handle, 0, self.n, a.ctypes.data, b.ctypes.data, flags, ctypes.byref(h)))
+        return CommitmentKey(self.curve, h.value, self.n // 2, self.h, self.mont)
+
+    def scale(self, r, mont=False, precompute=False):
+        """`scale` (pedersen.rs:500-512): out[i] = r * self[i] (nmx_bases_scale).  r: 32 bytes on the host, canonical, or Montgomery
+        words with mont."""
+        a = _host_u8(r, 32)
+        assert a.size == 32, "r is one scalar"
+        h = ctypes.c_uint64(0)
+        flags = (L.SCALARS_MONT if mont else 0) | (L.BASES_PRECOMPUTE if precompute else 0)
+        _check(L.lib().nmx_bases_scale(self.handle, 0, self.n, a.ctypes.data, flags, ctypes.byref(h)))
+        return CommitmentKey(self.curve, h.value, self.n, self.h, self.mont)
+
     def shard_plan(self, offset=0, n=None):
         """[(device, offset inside the shard, count)] for a call over key[offset, offset + n), from the layout the
         REGISTERED key has (nmx_bases_shard_plan) -- the plan to cut shard-resident scalar pieces by.  (A generated key is
