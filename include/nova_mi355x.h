@@ -756,6 +756,42 @@ typedef int (*nmx_ipa_transcript_fn)(void* ctx, const uint8_t* L_xy64, int L_is_
                                      uint8_t* r32_out);
 int nmx_ipa_prove(uint64_t ck_handle, const void* ck_c_xy64, const void* a, const void* b, size_t n, uint32_t flags,
                   nmx_ipa_transcript_fn transcript, void* ctx, uint8_t* out_L, uint8_t* out_R, uint8_t* out_is_inf, uint8_t* out_a_hat);
+/* ---- HyperKZG's evaluation argument (the evaluation engine of the primary curve) -------------------------------------------------
+ * EvaluationEngineTrait::prove of HyperKZG (src/provider/hyperkzg.rs:926-1116: prove :1076-1116, kzg_open_batch :1007-1072, kzg_open
+ * :1002-1004, div_by_monomial :961-999) as one call, n = 2^ell >= 2 evaluations of hat_P:
+ *   1. the ell - 1 pair folds with x[ell - i - 1] (:1085-1095) into the call's workspace     2. one fused batch commitment of the folded
+ *   polynomials over the registered key (:1100, blinding 0)     3. STAGE 0 of the callback with the ell - 1 commitments -> r
+ *   (compute_challenge, :861-865)     4. u = [r, -r, r^2] (:1106)     5. the whole v matrix in one launch (:1049-1056)     6. STAGE 1 with
+ *   the 3 ell scalars of v -> q (get_batch_challenge, :869-880)     7. the three quotients of B = sum q^i f_i in one pass
+ *   (nmx_poly_lincomb_quotients; :1059-1065)     8. one batch commitment of the three quotients of n - 1 coefficients (:1062-1065)
+ *   9. STAGE 2 with the three w, so that the caller's transcript reaches the state the verifier's will have
+ *   (verifier_second_challenge, :1069); whatever the callback writes at this stage is ignored.
+ * The pairing check and tau_H stay the caller's.
+ *   ck_handle   a registered key on ONE device with at least n points, of any of the four curves (the field is the curve's scalar
+ *               field); unknown, shorter than n or sharded over several devices: NMX_E_HANDLE
+ *   hat_P       n elements; host, or HBM with NMX_SCALARS_DEVICE; canonical, or Montgomery limbs with NMX_SCALARS_MONT (then the
+ *               challenges and v are Montgomery too).  Never modified.
+ *   point       host, ell elements, point[0] first as the reference's x; an element >= p: NMX_E_SCALAR_RANGE
+ *   transcript  (ctx, stage, data, count, is_inf, out32) -> 0, or non-zero: NMX_E_ARG.  Stage 0: data = count = ell - 1 points, affine
+ *               canonical x || y of 64 bytes each (NMX_BASES_MONT: Montgomery limbs), is_inf[i] = point i is the identity; ell = 1:
+ *               count = 0 (the reference absorbs the empty vector and squeezes).  Stage 1: data = count = 3 ell scalars of 32 bytes,
+ *               row-major (row i = f_i at r, -r, r^2), is_inf = NULL.  Stage 2: data = 3 points, is_inf as in stage 0.  A challenge
+ *               written to out32 (stages 0 and 1, in the scalars' form) >= p: NMX_E_SCALAR_RANGE; r = 0 and q = 0 are legal (nothing
+ *               is inverted).  The callback runs on the calling thread and MUST NOT synchronise the device (no nmx_sync, no
+ *               hipDeviceSynchronize: the restriction of the sum-check callbacks).
+ *   out_com, out_com_is_inf   ell - 1 points of 64 bytes and their identity bytes (out_com may be NULL when ell = 1, out_com_is_inf always)
+ *   out_v       ell x 3 scalars;   out_w, out_w_is_inf   3 points and their identity bytes (out_w_is_inf may be NULL)
+ * Flags: NMX_SCALARS_MONT, NMX_SCALARS_DEVICE, NMX_ASYNC (accepted; the call is synchronous), NMX_BASES_MONT (the form of the points
+ * given to the callback and written out); anything else NMX_E_ARG.  n not a power of two or n < 2 (the reference's `0..ell - 1`
+ * underflows at ell = 0), a NULL among hat_P, point, transcript, out_com (ell > 1), out_v, out_w: NMX_E_ARG, before a device or a key is
+ * touched.  On an error the outputs written so far are unspecified and nothing of the call still runs.  Synchronous, ordered behind the
+ * calling thread's NMX_ASYNC calls; thread-safe like nmx_ipa_prove.  Option kzg_fused_quotients: 1 runs step 7 as the one pass, 0 as
+ * nmx_field_lincomb_powers + 3 x nmx_poly_suffix_horner, 2 (the default) chooses by size -- the pass from n = 2^20 on, where it is the
+ * faster of the two (docs/measurements.md).  The same bytes every way. */
+typedef int (*nmx_transcript_fn_kzg)(void* ctx, int stage, const uint8_t* data, size_t count, const uint8_t* is_inf, uint8_t* out32);
+typedef nmx_transcript_fn_kzg nmx_kzg_transcript_fn; /* the same type under the name that reads like nmx_ipa_transcript_fn */
+int nmx_hyperkzg_prove(uint64_t ck_handle, const void* hat_P, size_t n, const void* point, uint32_t flags, nmx_transcript_fn_kzg transcript,
+                       void* ctx, uint8_t* out_com, uint8_t* out_com_is_inf, uint8_t* out_v, uint8_t* out_w, uint8_t* out_w_is_inf);
 /* InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390), reached through EvaluationEngine::verify (:80-99) from
  * RelaxedR1CSSNARK::verify (src/spartan/snark.rs:384, ppsnark.rs:1645) inside CompressedSNARK::verify (src/nova/mod.rs:912), from the
  * point where the caller's transcript has produced its challenges: the verifier's transcript never waits for the device (it absorbs
@@ -800,6 +836,25 @@ int nmx_field_lincomb_powers(int field, const void* const* vecs, const size_t* l
  * (NMX_E_ARG for device-resident vectors that do: every out[i] depends on all later coefficients while other waves still
  * read them).  Coefficients may be any 256-bit words; the outputs are canonical (< p). */
 int nmx_poly_suffix_horner(int field, const void* f, size_t n, const void* u, uint32_t flags, void* out);
+/* The three openings of kzg_open_batch (src/provider/hyperkzg.rs:1007-1072) as ONE pass over the folded polynomials: with
+ * B[t] = sum_{i : lens[i] > t} q^i polys[i][t] for t < n_out = max lens[i] (B is :1059; it is summed on the fly and never stored) and
+ * m <= 3 points u_j,
+ *     outs[j][t] = sum_{s >= t} B[s] u_j^(s - t),  t < n_out
+ * so outs[j][0] = B(u_j) (poly_eval, :1011-1020) and outs[j][1..n_out) is the quotient of div_by_monomial(B, u_j) (:961-999).  The
+ * outputs are canonical, so they equal nmx_field_lincomb_powers followed by nmx_poly_suffix_horner per point byte for byte; a lane reads
+ * only the vectors long enough to reach its index.  u_j = 0, q = 0 and equal points are fine.  Mercury's quot_f is the same pattern with
+ * k = 2, m = 1.
+ *   polys, lens, q, points, outs   host arrays; k vectors of lens[i] >= 0 elements, coefficients low to high, a word is ANY 256-bit value
+ *               read mod p (OPERAND WORDS above); q: 32 bytes; points: m x 32 bytes; outs: m vectors of n_out elements
+ *   flags       NMX_SCALARS_DEVICE (the vectors and the outputs are in HBM), NMX_SCALARS_MONT (q, the points and the words are
+ *               Montgomery limbs), NMX_ASYNC (HBM operands); anything else NMX_E_ARG
+ * k = 0, m = 0, a NULL argument, a field_id that is none of NMX_F_* (not spelled `field`, as for nmx_field_gather), an outs[j] that overlaps an input or another output: NMX_E_ARG;
+ * m > 3, k > 4096 or a vector of 2^31 elements or more: NMX_E_TOO_LARGE; q or a point >= p: NMX_E_SCALAR_RANGE.  All found before a
+ * device is leased; nothing written.  Options (nmx_set_option; none changes a byte of a result): kzg_quot_chunk (coefficients per lane
+ * of the pass over the inputs, 0 = 4, or 8), kzg_quot_scratch (1, the default: the first pass stores B in workspace and the second reads
+ * it back; 0: the second sums it again). */
+int nmx_poly_lincomb_quotients(int field_id, const void* const* polys, const size_t* lens, size_t k, const void* q, const void* points, size_t m,
+                               uint32_t flags, void* const* outs);
 /* HyperKZG's evaluation matrix (src/provider/hyperkzg.rs:1011-1020 `poly_eval`, called for every folded polynomial at
  * the three points r, -r, r^2, :1049-1056): out[i * m + j] = polys[i](points[j]) for k polynomials of any lengths
  * (coefficients low to high; an empty polynomial evaluates to 0) at m <= 4 points, all in one launch.  `polys`, `lens`,

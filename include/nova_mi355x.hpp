@@ -512,6 +512,62 @@ inline bool verify(const CommitmentKey& ck, const Affine& ck_c, const Point& com
 }
 }  // namespace ipa
 
+// HyperKZG's evaluation argument (src/provider/hyperkzg.rs:926-1116) over the C ABI's one call.  `Transcript` is the caller's: any type
+// with `Scalar stage(int stage, const uint8_t* data, size_t count, const uint8_t* is_inf)` -- stage 0 absorbs the count = ell - 1
+// commitments (64 bytes each, is_inf[i]: point i is the identity) and squeezes r (:861-865), stage 1 absorbs the count = 3 ell scalars of
+// v and squeezes q (:869-880), stage 2 absorbs the three w (:1069; what it returns is ignored).  It runs on the calling thread and must not
+// synchronise the device.  The pairing check and tau_H stay the caller's.
+namespace hyperkzg {
+using provider::check;
+using provider::CommitmentKey;
+using provider::Point;
+using provider::Scalar;
+
+struct EvaluationArgument {  // com, w, v (:310-330)
+  std::vector<Point> com;
+  std::vector<std::array<Scalar, 3>> v;
+  std::array<Point, 3> w{};
+};
+namespace detail {
+template <class Transcript> int stage_cb(void* ctx, int stage, const uint8_t* data, size_t count, const uint8_t* is_inf, uint8_t* out) {
+  try {
+    const Scalar c = static_cast<Transcript*>(ctx)->stage(stage, data, count, is_inf);
+    std::copy(c.begin(), c.end(), out);
+    return 0;
+  } catch (...) {
+    return 1;  // never let an exception cross the C frame: the call fails with NMX_E_ARG
+  }
+}
+// hat_P: n = 2^ell elements where `flags` says; point: ell coordinates, point[0] first as the reference's x
+inline EvaluationArgument prove_call(const CommitmentKey& ck, const void* hat_P, size_t n, const std::vector<Scalar>& point, uint32_t flags,
+                                     nmx_transcript_fn_kzg cb, void* ctx) {
+  size_t ell = 0;
+  while (((size_t)1 << ell) < n) ell++;
+  if (n < 2 || point.size() != ell) throw std::invalid_argument("hyperkzg::prove: n = 2^ell >= 2 and ell coordinates");
+  std::vector<uint8_t> com(64 * ell), com_inf(ell), v(96 * ell), w(192), w_inf(3);
+  check(nmx_hyperkzg_prove(ck.handle(), hat_P, n, point.data(), flags | (ck.mont() ? NMX_BASES_MONT : 0u), cb, ctx, com.data(), com_inf.data(),
+                           v.data(), w.data(), w_inf.data()));
+  EvaluationArgument out;
+  out.com.resize(ell - 1), out.v.resize(ell);
+  for (size_t i = 0; i + 1 < ell; i++) {
+    std::copy(com.begin() + 64 * i, com.begin() + 64 * i + 64, out.com[i].xy.begin());
+    out.com[i].is_inf = com_inf[i] != 0;
+  }
+  for (size_t i = 0; i < ell; i++)
+    for (size_t j = 0; j < 3; j++) std::copy(v.begin() + 96 * i + 32 * j, v.begin() + 96 * i + 32 * j + 32, out.v[i][j].begin());
+  for (size_t j = 0; j < 3; j++) {
+    std::copy(w.begin() + 64 * j, w.begin() + 64 * j + 64, out.w[j].xy.begin());
+    out.w[j].is_inf = w_inf[j] != 0;
+  }
+  return out;
+}
+}  // namespace detail
+template <class Transcript>
+EvaluationArgument prove(const CommitmentKey& ck, const std::vector<Scalar>& hat_P, const std::vector<Scalar>& point, Transcript& tr, bool mont = false) {
+  return detail::prove_call(ck, hat_P.data(), hat_P.size(), point, mont ? NMX_SCALARS_MONT : 0u, &detail::stage_cb<Transcript>, &tr);
+}
+}  // namespace hyperkzg
+
 // Hosts that keep their vectors in HBM between provider calls (INTEGRATION.md sections 2b-2e: the patched r1cs/mod.rs, nifs.rs,
 // snark.rs): the same operations over device pointers.  Thin by design -- each function is one C call with NMX_SCALARS_DEVICE (and
 // NMX_ASYNC where the host does not look at the result before its next synchronous call); allocation is the host's business
@@ -797,6 +853,19 @@ inline IpaProof ipa_prove(const CommitmentKey& ck, const Affine& ck_c, const voi
   check(nmx_ipa_prove(ck.handle(), ck_c.data(), a, b, n, kDev, cb, ctx, p.L.data(), p.R.data(), p.inf.data(), p.a_hat.data()));
   p.L.resize(64 * rounds), p.R.resize(64 * rounds), p.inf.resize(2 * rounds);
   return p;
+}
+// The three openings of kzg_open_batch (hyperkzg.rs:1007-1072) in one pass over HBM-resident vectors: outs[j][t] = sum_{s >= t} B[s] pts[j]^(s - t)
+// with B = sum_i q^i polys[i] (never stored); outs: pts.size() <= 3 vectors of max(lens) elements.  Mercury's quot_f is k = 2, m = 1.
+inline void lincomb_quotients(int field, const std::vector<const void*>& polys, const std::vector<size_t>& lens, const Scalar& q,
+                              const std::vector<Scalar>& pts, const std::vector<void*>& outs) {
+  if (outs.size() != pts.size() || polys.size() != lens.size()) throw std::invalid_argument("lincomb_quotients: one output per point, one length per vector");
+  check(nmx_poly_lincomb_quotients(field, polys.data(), lens.data(), polys.size(), q.data(), pts.data(), pts.size(), kDev, outs.data()));
+}
+// EvaluationEngineTrait::prove of HyperKZG (hyperkzg.rs:926-1116) over an HBM-resident hat_P of n = 2^ell elements; the
+// callback runs on the calling thread and must not synchronise the device
+inline hyperkzg::EvaluationArgument hyperkzg_prove(const CommitmentKey& ck, const void* hat_P, size_t n, const std::vector<Scalar>& point,
+                                                   nmx_transcript_fn_kzg cb, void* ctx, bool mont = false) {
+  return hyperkzg::detail::prove_call(ck, hat_P, n, point, kDev | (mont ? NMX_SCALARS_MONT : 0u), cb, ctx);
 }
 // InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) over an HBM-resident b_vec of n elements
 inline bool ipa_verify(const CommitmentKey& ck, const Affine& ck_c, const provider::Point& comm_a, const Scalar& c, const void* b, size_t n,

@@ -32,6 +32,9 @@ TRANSCRIPT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(c
 # nmx_ipa_transcript_fn: (ctx, L xy64, L is the identity, R xy64, R is the identity, challenge out) -> 0
 IPA_TRANSCRIPT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.POINTER(ctypes.c_uint8), ctypes.c_int,
                                      ctypes.POINTER(ctypes.c_uint8), ctypes.c_int, ctypes.POINTER(ctypes.c_uint8))
+# nmx_transcript_fn_kzg: (ctx, stage, data, count, is_inf or NULL, challenge out) -> 0
+KZG_TRANSCRIPT_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int, ctypes.POINTER(ctypes.c_uint8), ctypes.c_size_t,
+                                     ctypes.POINTER(ctypes.c_uint8), ctypes.POINTER(ctypes.c_uint8))
 
 _lib = None
 
@@ -144,6 +147,8 @@ def lib():
     L.nmx_ppsnark_spark_repr.argtypes = [vp, sz, sz, u32, vp, vp, vp, vp, vp]
     L.nmx_masked_eq_evals.argtypes = [i, vp, sz, sz, u32, vp]
     L.nmx_ipa_prove.argtypes = [u64, vp, vp, vp, sz, u32, IPA_TRANSCRIPT_FN, vp, vp, vp, vp, vp]
+    L.nmx_hyperkzg_prove.argtypes = [u64, vp, sz, vp, u32, KZG_TRANSCRIPT_FN, vp, vp, vp, vp, vp, vp]
+    L.nmx_poly_lincomb_quotients.argtypes = [i, vp, vp, sz, vp, vp, sz, u32, vp]
     L.nmx_ipa_verify.argtypes = [u64, vp, vp, i, vp, vp, sz, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.nmx_set_profiling.argtypes = [i]
     L.nmx_profile_last.argtypes = [ctypes.POINTER(ctypes.c_float), i]

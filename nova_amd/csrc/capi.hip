@@ -2604,6 +2604,38 @@ int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, s
   });
 }
 
+// ---- HyperKZG's batched multi-point quotients (hyperkzg.hpp; src/provider/hyperkzg.rs:1007-1072) ------------------------------------------
+// Everything that can be refused is refused before a device is leased: a refused call needs no device, launches nothing, writes nothing.
+int nmx_poly_lincomb_quotients(int field_id, const void* const* polys, const size_t* lens, size_t k, const void* q, const void* points, size_t m,
+                               uint32_t flags, void* const* outs) {
+  return guarded([&] {
+    require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_ASYNC)) == 0, NMX_E_ARG,
+            "nmx_poly_lincomb_quotients: only NMX_SCALARS_MONT, NMX_SCALARS_DEVICE and NMX_ASYNC apply");
+    with_field(field_id, [](auto) {});
+    require(k >= 1 && m >= 1 && polys && lens && q && points && outs, NMX_E_ARG, "nmx_poly_lincomb_quotients: k, m >= 1 and no null argument");
+    require(m <= 3 && k <= 4096, NMX_E_TOO_LARGE, "nmx_poly_lincomb_quotients: at most 3 points and 4096 vectors per call");
+    size_t n_out = 0;
+    for (size_t i = 0; i < k; i++) {
+      require(lens[i] < (1ull << 31), NMX_E_TOO_LARGE, "nmx_poly_lincomb_quotients: vector too long");
+      require(polys[i] || lens[i] == 0, NMX_E_ARG, "nmx_poly_lincomb_quotients: null vector");
+      n_out = lens[i] > n_out ? lens[i] : n_out;
+    }
+    std::vector<ByteSpan> outs_sp;
+    for (size_t j = 0; j < m; j++) {
+      require(outs[j] || n_out == 0, NMX_E_ARG, "nmx_poly_lincomb_quotients: null output");
+      for (size_t i = 0; i < k; i++)
+        require(!elems_overlap(outs[j], n_out, polys[i], lens[i]), NMX_E_ARG, "nmx_poly_lincomb_quotients: an output overlaps an input");
+      if (n_out) outs_sp.push_back(span_of(outs[j], n_out));
+    }
+    require_disjoint(outs_sp, "nmx_poly_lincomb_quotients: two outputs overlap");
+    require_canonical(field_id, q, 1, "nmx_poly_lincomb_quotients: q >= field modulus");
+    require_canonical(field_id, points, m, "nmx_poly_lincomb_quotients: a point >= field modulus");
+    if (n_out == 0) return;
+    CtxLease L;
+    fv_lincomb_quotients(*L.c, field_id, polys, lens, k, q, points, m, flags, outs, false);
+  });
+}
+
 // ---- NeutronNova's folding step (neutron.hpp; src/neutron/nifs.rs:29-186, src/neutron/relation.rs:83-97 and :131-156, power.rs:62-86) -----
 // Everything that can be refused is refused before a device is leased: a refused call needs no device, launches nothing, writes nothing.
 static void neutron_check_flags(int field_id, uint32_t flags, uint32_t allowed, const char* msg) {
@@ -3272,8 +3304,8 @@ struct CallScratch {
   void* owned = nullptr;
   size_t used = 0;
   hipEvent_t ev = nullptr;
-  CallScratch(Ctx& c, size_t total) {
-    if (total <= kAuxMax) {
+  CallScratch(Ctx& c, size_t total, size_t aux_max = kAuxMax) {
+    if (total <= aux_max) {
       aux_reserve(c, total);
       base = c.aux;
     } else {
@@ -3386,6 +3418,121 @@ int nmx_ipa_prove(uint64_t ck_handle, const void* ck_c_xy64, const void* a, cons
       fv_ipa_last(c, field, a_cur, r, rinv, sflags, dout, out_a_hat);  // the last round's vector has two elements
     } catch (...) {
       (void)hipStreamSynchronize(c.stream);  // nothing of this call still reads the caller's vectors
+      throw;
+    }
+  });
+}
+
+// EvaluationEngineTrait::prove of HyperKZG (src/provider/hyperkzg.rs:1076-1116 with kzg_open_batch, :1007-1072) as one call: the pair
+// folds into the call's own workspace, one fused batch commitment, r from the callback, u = [r, -r, r^2], the v matrix in one launch, q
+// from the callback, the three quotients of B = sum q^i f_i in one pass over the folded polynomials (hyperkzg.hpp; option
+// kzg_fused_quotients = 0: lincomb_powers + 3 x suffix Horner, the same bytes), one batch commitment of the quotients.  The workspace
+// (the folds, three n-element quotient vectors, a staged host polynomial) has to outlive the MSMs, which re-carve the context's arena:
+// it lives in the context's aux buffer, which this call lets grow to kKzgAuxMax (a 2^20 proof needs 160 MiB; an allocation per call
+// would cost more than the quotient pass).
+static constexpr size_t kKzgAuxMax = (size_t)1 << 30;
+// Option kzg_fused_quotients = 2 (the default): the fused pass from this many coefficients on.  Measured (docs/measurements.md): at 2^20 the
+// pass takes 0.32-0.38 ms against 0.40-0.41 ms for lincomb_powers + 3 x suffix Horner; at 2^19 0.35-0.37 against 0.31, at 2^14 0.22-0.25
+// against 0.19 -- below 2^20 both are bound by their launches and the composed division has fewer of them.
+static constexpr size_t kKzgFusedMinN = (size_t)1 << 20;
+int nmx_hyperkzg_prove(uint64_t ck_handle, const void* hat_P, size_t n, const void* point, uint32_t flags, nmx_transcript_fn_kzg transcript,
+                       void* ctx, uint8_t* out_com, uint8_t* out_com_is_inf, uint8_t* out_v, uint8_t* out_w, uint8_t* out_w_is_inf) {
+  return guarded([&] {
+    require(transcript != nullptr, NMX_E_ARG, "null transcript callback");
+    require(hat_P && point && out_v && out_w, NMX_E_ARG, "null argument");
+    require(!(flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_ASYNC | NMX_BASES_MONT)), NMX_E_ARG, "unsupported flag");
+    require(n >= 2 && (n & (n - 1)) == 0, NMX_E_ARG, "n must be a power of two, at least 2");  // `0..ell - 1` underflows at ell = 0 (:1085)
+    require(n < ((size_t)1 << 31), NMX_E_TOO_LARGE, "polynomial too long");
+    size_t ell = 0;
+    while (((size_t)1 << ell) < n) ell++;
+    require(ell == 1 || out_com, NMX_E_ARG, "null argument");
+    ensure_init();
+    auto bs = lookup(ck_handle);
+    require(bs->parts.empty(), NMX_E_HANDLE, "nmx_hyperkzg_prove: a key sharded over several devices is not supported");
+    require(n <= bs->n, NMX_E_HANDLE, "ck shorter than the polynomial");
+    const CurveOps& o = ops(bs->curve);
+    const int field = o.scalar_field;
+    require_canonical(field, point, ell, "nmx_hyperkzg_prove: a coordinate of the point >= field modulus");
+    const bool dev = (flags & NMX_SCALARS_DEVICE) != 0, mont = (flags & NMX_SCALARS_MONT) != 0;
+    const uint32_t sflags = (flags & NMX_SCALARS_MONT) | NMX_SCALARS_DEVICE;
+    const uint32_t mflags = (flags & (NMX_SCALARS_MONT | NMX_BASES_MONT)) | NMX_SCALARS_DEVICE;
+    const uint32_t fused_opt = G.kzg_fused_quotients.load(std::memory_order_relaxed);
+    const bool fused = fused_opt == 1 || (fused_opt == 2 && n >= kKzgFusedMinN);
+    CtxLease L;
+    Ctx& c = *L.c;
+    // the call's device state, outside the arena the MSMs re-carve: [hat_P staged] folds n/2 .. 2, three quotient vectors, [B]
+    const size_t full = pad256(n * 32);
+    size_t total = (dev ? 0 : full) + 3 * full + (fused ? 0 : full) + 256;
+    for (size_t i = 1; i < ell; i++) total += pad256((n >> i) * 32);
+    CallScratch own(c, total, kKzgAuxMax);
+    try {
+      std::vector<const void*> polys(ell);
+      std::vector<size_t> lens(ell);
+      if (dev) {
+        polys[0] = hat_P;
+      } else {
+        uint32_t* s = own.carve(full);
+        HIPCHK(hipMemcpyAsync(s, hat_P, n * 32, hipMemcpyHostToDevice, c.stream));
+        polys[0] = s;
+      }
+      lens[0] = n;
+      for (size_t i = 1; i < ell; i++) polys[i] = own.carve(pad256((n >> i) * 32)), lens[i] = n >> i;
+      uint32_t* quot[3] = {own.carve(full), own.carve(full), own.carve(full)};
+      uint32_t* Bvec = fused ? nullptr : own.carve(full);
+      // 1. Pi[j] = x[ell - i - 1] * (P[2j + 1] - P[2j]) + P[2j], i = 0 .. ell - 2 (:1085-1095)
+      if (ell > 1) {
+        std::vector<uint8_t> xs(32 * (ell - 1));
+        for (size_t i = 0; i + 1 < ell; i++) memcpy(xs.data() + 32 * i, (const uint8_t*)point + 32 * (ell - i - 1), 32);
+        fv_fold_chain(c, field, polys[0], n, xs.data(), ell - 1, sflags | NMX_ASYNC, (void* const*)(polys.data() + 1));
+      }
+      // 2. com = batch_commit(polys[1..]) (:1100); the helper lanes of the batch are ordered behind the folds by the mark
+      std::vector<uint8_t> com(64 * ell), com_inf(ell, 0);
+      if (ell > 1) {
+        async_mark(c);
+        batch_impl(*bs, 0, bs->n, polys.data() + 1, lens.data() + 1, ell - 1, mflags, com.data(), com_inf.data(), c);
+        memcpy(out_com, com.data(), 64 * (ell - 1));
+        if (out_com_is_inf) memcpy(out_com_is_inf, com_inf.data(), ell - 1);
+      }
+      // 3. r (:1105, compute_challenge :861-865)
+      uint8_t r[32], qc[32], ignored[32], us[96];
+      require(transcript(ctx, 0, com.data(), ell - 1, com_inf.data(), r) == 0, NMX_E_ARG, "the transcript callback failed");
+      require_canonical(field, r, 1, "nmx_hyperkzg_prove: the challenge r >= field modulus");
+      // 4. u = [r, -r, r^2] (:1106)
+      with_field(field, [&](auto F) {
+        using H = HostFp4<decltype(F)::value>;
+        const H hr = mont ? H::from_mont256(r) : H::from_canonical(r);
+        const H hu[3] = {hr, H::zero() - hr, hr * hr};
+        for (int j = 0; j < 3; j++) {
+          if (mont) hu[j].to_mont256(us + 32 * j);
+          else hu[j].to_canonical(us + 32 * j);
+        }
+      });
+      // 5. v[i][j] = f_i(u_j) (:1049-1056), 6. q (:1058, get_batch_challenge :869-880)
+      std::vector<uint8_t> v(96 * ell);
+      fv_eval_multi(c, field, polys.data(), lens.data(), ell, us, 3, sflags, v.data());
+      memcpy(out_v, v.data(), 96 * ell);
+      require(transcript(ctx, 1, v.data(), 3 * ell, nullptr, qc) == 0, NMX_E_ARG, "the transcript callback failed");
+      require_canonical(field, qc, 1, "nmx_hyperkzg_prove: the challenge q >= field modulus");
+      // 7. the three openings of B = sum q^i f_i (:1059-1065): quot[j][0] = B(u_j), quot[j][1..] = the quotient
+      void* const outs[3] = {quot[0], quot[1], quot[2]};
+      if (fused) {
+        fv_lincomb_quotients(c, field, polys.data(), lens.data(), ell, qc, us, 3, sflags, outs, true);
+      } else {
+        fv_lincomb(c, field, polys.data(), lens.data(), ell, qc, n, sflags, Bvec);
+        for (int j = 0; j < 3; j++) fv_suffix_horner(c, field, Bvec, n, us + 32 * j, sflags, quot[j]);
+      }
+      // 8. w = the commitments of the three quotients, n - 1 coefficients each (:1002-1004)
+      const void* hs[3] = {quot[0] + 8, quot[1] + 8, quot[2] + 8};
+      const size_t hl[3] = {n - 1, n - 1, n - 1};
+      uint8_t w[192], w_inf[3] = {0, 0, 0};
+      async_mark(c);
+      batch_impl(*bs, 0, bs->n, hs, hl, 3, mflags, w, w_inf, c);
+      memcpy(out_w, w, 192);
+      if (out_w_is_inf) memcpy(out_w_is_inf, w_inf, 3);
+      // 9. the caller's transcript absorbs w (verifier_second_challenge, :1069); what it squeezes is not used here
+      require(transcript(ctx, 2, w, 3, w_inf, ignored) == 0, NMX_E_ARG, "the transcript callback failed");
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);  // nothing of this call still reads the caller's polynomial or the workspace
       throw;
     }
   });
@@ -3710,6 +3857,15 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "horner_window") G.horner_window = value ? value : 64u;
     else if (n == "horner_sub") G.horner_sub = value;
     else if (n == "mercury_seg_rows") G.mercury_seg_rows = value;
+    else if (n == "kzg_fused_quotients") {
+      require(value <= 2, NMX_E_ARG, "kzg_fused_quotients: 0 = lincomb_powers + 3 x suffix Horner, 1 = the fused pass, 2 = by size");
+      G.kzg_fused_quotients = value;
+    }
+    else if (n == "kzg_quot_chunk") {
+      require(value == 0 || value == 4 || value == 8, NMX_E_ARG, "kzg_quot_chunk: coefficients per lane of the quotient pass, 0 (= 4), 4 or 8");
+      G.kzg_quot_chunk = value;
+    }
+    else if (n == "kzg_quot_scratch") G.kzg_quot_scratch = value ? 1u : 0u;
     else if (n == "neutron_max_blocks") G.neutron_max_blocks = value;
     else if (n == "fixed_base_c") {
       require(value >= kFbMinC && value <= kFbMaxC, NMX_E_ARG, "fixed_base_c: window width of the fixed-base key kernels, 4 .. 16");

@@ -1731,5 +1731,6 @@ void fv_bind(Ctx& c, int field, const void* z, size_t z_len, size_t lo_off, size
 
 #include "r1cs_eval.hpp"
 #include "mercury.hpp"
+#include "hyperkzg.hpp"
 #include "ppsnark_oracles.hpp"
 #include "ppsnark_key.hpp"

@@ -337,7 +337,10 @@ struct Global {
   std::atomic<uint32_t> horner_sub{0};            // option horner_sub: 512-coefficient sub-tiles per wave of the single-pass scan (0 = by size, 1, 2, 4)
   std::atomic<uint32_t> horner_spin_limit{0};     // option horner_spin_limit: polls before a wave of the scan gives up (0 = 2^22; tests set 1 to force the fall-back)
   std::atomic<uint32_t> horner_window{64};        // option horner_window: tiles per look-back round of the single-pass scan (tests: 1 .. 63 force the multi-round path)
-  std::atomic<uint32_t> mercury_seg_rows{0};      // option mercury_seg_rows: rows per segment of Mercury's division kernels (mercury.hpp mercury_plan; 0 = by size; tests force the multi-segment path at tiny shapes)
+  std::atomic<uint32_t> kzg_fused_quotients{2};   // option kzg_fused_quotients: nmx_hyperkzg_prove's three openings: 1 = ONE pass over the folded polynomials (hyperkzg.hpp), 0 = lincomb_powers + 3 x suffix Horner, 2 = by size (the pass from kKzgFusedMinN coefficients, capi.hip).  Same bytes either way
+  std::atomic<uint32_t> kzg_quot_chunk{0};        // option kzg_quot_chunk: coefficients per lane of that pass's level 0 (0 / 4 = 4, 8 = 8)
+  std::atomic<uint32_t> kzg_quot_scratch{1};      // option kzg_quot_scratch: 1 = the heads pass stores B and the walk reads it back, 0 = the walk sums it again
+  std::atomic<uint32_t> mercury_seg_rows{0};     // option mercury_seg_rows: rows per segment of Mercury's division kernels (mercury.hpp mercury_plan; 0 = by size; tests force the multi-segment path at tiny shapes)
   std::atomic<uint32_t> fixed_base_c{kFbDefaultC};         // option fixed_base_c: window width of the fixed-base key kernels (fixed_base.hpp; 4 .. 16, default 8: docs/measurements.md)
   std::atomic<uint32_t> derive_lmax{0};            // option derive_lmax: the longest run one lane of nmx_bases_derive_by_address adds (derive_key.hpp; 0 = derive_default_lmax, 2 .. 1024; tests reach the split and fold passes with few points)
   std::atomic<uint32_t> neutron_max_blocks{0};    // option neutron_max_blocks: the largest grid of the two NeutronNova sums (neutron.hpp neutron_blocks; 0 = by size; tests force a wave's loop over tiles at tiny shapes)
@@ -904,6 +907,11 @@ void fv_r1cs_evaluate(Ctx&, int field, const CsrView* mats, size_t k, const void
 void fv_mercury_h_poly(Ctx&, int field, const void* f, size_t n_rows, size_t n_cols, const void* eq_col, uint32_t flags, void* out_h);
 void fv_mercury_divide_by_binomial(Ctx&, int field, const void* f, size_t n_rows, size_t n_cols, const void* alpha, uint32_t flags,
                                    void* out_q, void* out_g);
+// HyperKZG's batched multi-point quotients (hyperkzg.hpp): out_j[t] = sum_{s >= t} B[s] u_j^(s - t), B = sum_i q^i f_i, m <= 3 points.
+// Vectors follow NMX_SCALARS_DEVICE, q and the points are host pointers; NMX_ASYNC with HBM operands.  chain: a step of a longer call on
+// the same stream (nothing waited for, nothing marked).  Shapes, NULLs and overlaps are the caller's to check.
+void fv_lincomb_quotients(Ctx&, int field, const void* const* polys, const size_t* lens, size_t k, const void* q, const void* points,
+                          size_t m, uint32_t flags, void* const* outs, bool chain);
 // ppsnark's lookup gather and fused logUp oracles (ppsnark_oracles.hpp).  Vectors follow NMX_SCALARS_DEVICE, gamma and r are host pointers;
 // synchronous.  fv_gather: false when an address is not below n_mem (or, Montgomery words, not below p); fv_ppsnark_mem_oracles: false when
 // some T + r or W + r is zero.  Shapes, NULLs, the scalars' range and overlaps are the caller's to check.

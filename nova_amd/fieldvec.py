@@ -401,6 +401,31 @@ def suffix_horner(field, f, u, mont=False):
     return out
 
 
+def lincomb_quotients(field, polys, q, points, mont=False, async_=False):
+    """The three openings of kzg_open_batch (hyperkzg.rs:1007-1072) in one pass (nmx_poly_lincomb_quotients): with B = sum_i q^i polys[i]
+    (ragged lengths, never stored), returns [out_j for the m <= 3 points u_j], out_j[t] = sum_{s >= t} B[s] u_j^(s - t) over
+    max len(polys[i]) elements: out_j[0] = B(u_j), out_j[1:] = the quotient of div_by_monomial(B, u_j).  Byte-identical to
+    lincomb_powers + suffix_horner per point.  Host arrays or CUDA tensors (all on the same side)."""
+    import ctypes
+    k = len(polys)
+    pts = _host_u8(points, 32)
+    m = pts.size // 32
+    parts = [_vec(f) if len(f) else (None, 0, None, None) for f in polys]
+    devs = {pt[2] for pt in parts if pt[2] is not None}
+    assert len(devs) <= 1, "all vectors on the same side"
+    dev = bool(devs) and devs.pop()
+    n_out = max([pt[1] for pt in parts], default=0)
+    like = next((f for f, pt in zip(polys, parts) if pt[2] is not None), None)
+    ptrs = (ctypes.c_void_p * max(k, 1))(*[pt[0] for pt in parts])
+    lens = (ctypes.c_size_t * max(k, 1))(*[pt[1] for pt in parts])
+    outs = [_out_like(dev, n_out, like) for _ in range(m)]
+    po = (ctypes.c_void_p * max(m, 1))(*[o[0] for o in outs])
+    qq = _chal(q)
+    _check(L.lib().nmx_poly_lincomb_quotients(field, ptrs, lens, k, qq.ctypes.data, pts.ctypes.data if m else None, m,
+                                              _flags(dev, mont, async_), po))
+    return [o[1] for o in outs]
+
+
 def poly_eval_multi(field, polys, points, mont=False):
     """[[f_i(u_j) for j] for i] in one launch (nmx_poly_eval_multi): HyperKZG's v matrix, hyperkzg.rs:1049-1056."""
     import ctypes

@@ -604,6 +604,52 @@ def ipa_prove(ck, ck_c_xy64, a, b, transcript, mont=False, ctx=None):
             [(bool(oi[2 * j]), bool(oi[2 * j + 1])) for j in range(rounds)], ah.tobytes())
 
 
+def as_kzg_transcript(fn):
+    """fn(stage: int, data: bytes, count: int, is_inf: bytes or None) -> 32-byte challenge (ignored at stage 2), wrapped as
+    nmx_transcript_fn_kzg.  Stage 0: count points of 64 bytes (the commitments of the folded polynomials; absorb them and squeeze r,
+    hyperkzg.rs:861-865); stage 1: count scalars of 32 bytes (the v matrix, row-major; squeeze q, :869-880); stage 2: the three w
+    (absorb them, :1069).  The callback runs on the calling thread and must not synchronise the device."""
+    if isinstance(fn, L.KZG_TRANSCRIPT_FN):
+        return fn
+
+    def cb(_ctx, stage, data, count, is_inf, out):
+        try:
+            size = (32 if stage == 1 else 64) * count
+            ch = fn(int(stage), bytes(data[:size]), int(count), bytes(is_inf[:count]) if is_inf else None)
+            if ch is not None:
+                ctypes.memmove(out, ch, 32)
+            return 0
+        except Exception:                   # an exception must not cross the C frame: the call fails with NMX_E_ARG
+            import traceback
+            traceback.print_exc()
+            return 1
+    return L.KZG_TRANSCRIPT_FN(cb)
+
+
+def hyperkzg_prove(ck, hat_P, point, transcript, ctx=None, mont=False):
+    """EvaluationEngineTrait::prove of HyperKZG (src/provider/hyperkzg.rs:926-1116) as one call (nmx_hyperkzg_prove): `ck` a
+    CommitmentKey on one device with at least len(hat_P) points, hat_P the 2^ell >= 2 evaluations (a host array or a CUDA tensor,
+    never modified), point the ell coordinates (host, point[0] first as the reference's x), transcript a callable for
+    as_kzg_transcript or a KZG_TRANSCRIPT_FN (with ctx).  The callback runs on the calling thread and must not synchronise the device.
+    Returns (com, v, w): com = [(xy64, is_identity)] * (ell - 1), v = ell rows of three 32-byte scalars (f_i at r, -r, r^2),
+    w = [(xy64, is_identity)] * 3.  The pairing check stays the caller's."""
+    pp, n, dev, _kp = _scalar_arg(hat_P, 32)
+    ell = max(n.bit_length() - 1, 0)
+    pt = _host_u8(point, 32)
+    assert pt.size == 32 * ell, "point has log2(len(hat_P)) coordinates"
+    oc, oci = np.zeros(64 * max(ell - 1, 1), np.uint8), np.zeros(max(ell - 1, 1), np.uint8)
+    ov = np.zeros(96 * max(ell, 1), np.uint8)
+    ow, owi = np.zeros(192, np.uint8), np.zeros(3, np.uint8)
+    flags = dev | (L.SCALARS_MONT if mont else 0) | (L.BASES_MONT if ck.mont else 0)
+    cb = as_kzg_transcript(transcript)
+    _check(L.lib().nmx_hyperkzg_prove(ck.handle, pp, n, pt.ctypes.data if ell else None, flags, cb, ctx, oc.ctypes.data, oci.ctypes.data,
+                                      ov.ctypes.data, ow.ctypes.data, owi.ctypes.data))
+    cb_, vb, wb = oc.tobytes(), ov.tobytes(), ow.tobytes()
+    return ([(cb_[64 * j: 64 * j + 64], bool(oci[j])) for j in range(ell - 1)],
+            [[vb[96 * i + 32 * j: 96 * i + 32 * j + 32] for j in range(3)] for i in range(ell)],
+            [(wb[64 * j: 64 * j + 64], bool(owi[j])) for j in range(3)])
+
+
 def ipa_verify(ck, ck_c_xy64, comm_a, c, b, L_vec, R_vec, infs, a_hat, rs, mont=False, point=False, want_intermediates=False):
     """InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) over a registered Pedersen key, from the point where the caller's
     transcript has produced the round challenges `rs` (32 bytes each, round 0 first).  `comm_a`: a Commitment, (xy64, is_inf) or 64

@@ -40,6 +40,8 @@ def rust_type(ctype):
         return "NmxTranscriptFn"
     if t == "nmx_ipa_transcript_fn":
         return "NmxIpaTranscriptFn"
+    if t == "nmx_transcript_fn_kzg":
+        return "NmxTranscriptFnKzg"
     toks = re.findall(r"const|\*|[A-Za-z_][A-Za-z0-9_]*", t)
     # C declarator, left to right: [const] base [const] { * [const] }
     i, base_const = 0, False
@@ -146,6 +148,11 @@ def generate():
           "/// One round of the inner-product argument: absorb L and R (affine canonical x || y, and whether each is the identity), squeeze r.",
           "pub type NmxIpaTranscriptFn = unsafe extern \"C\" fn(ctx: *mut c_void, l_xy64: *const u8, l_is_inf: c_int, r_xy64: *const u8, r_is_inf: c_int,",
           "                                                     r32_out: *mut u8) -> c_int;",
+          "/// One stage of HyperKZG's evaluation argument (nmx_hyperkzg_prove): stage 0 absorbs `count` commitments of 64 bytes (`is_inf[i]`: point i is the",
+          "/// identity) and squeezes r, stage 1 absorbs `count` scalars of 32 bytes (`is_inf` null) and squeezes q, stage 2 absorbs the three w.  It must not",
+          "/// synchronise the device.",
+          "pub type NmxTranscriptFnKzg = unsafe extern \"C\" fn(ctx: *mut c_void, stage: c_int, data: *const u8, count: usize, is_inf: *const u8,",
+          "                                                     out32: *mut u8) -> c_int;",
           "",
           "#[link(name = \"nova_mi355x\")]",
           "extern \"C\" {"]
