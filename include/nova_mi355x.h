@@ -792,6 +792,54 @@ typedef int (*nmx_transcript_fn_kzg)(void* ctx, int stage, const uint8_t* data, 
 typedef nmx_transcript_fn_kzg nmx_kzg_transcript_fn; /* the same type under the name that reads like nmx_ipa_transcript_fn */
 int nmx_hyperkzg_prove(uint64_t ck_handle, const void* hat_P, size_t n, const void* point, uint32_t flags, nmx_transcript_fn_kzg transcript,
                        void* ctx, uint8_t* out_com, uint8_t* out_com_is_inf, uint8_t* out_v, uint8_t* out_w, uint8_t* out_w_is_inf);
+/* ---- Mercury's evaluation argument (the second evaluation engine of the primary curve) ---------------------------------------------
+ * EvaluationEngineTrait::prove of Mercury (src/provider/mercury.rs:891-1268 with batch_evaluation::generate_batch_evaluate_arg,
+ * :567-770) as one call: a constant-size proof of eight commitments and six scalars for n = 2^ell evaluations, ell >= 2
+ * (assert!(log_n > 1), :914).  Shape (:911-931): ell' = ell rounded up to even, b = 2^(ell' / 2), f viewed as n_rows x b with
+ * n_rows = n / b (b, or b / 2 when ell is odd); an odd ell gives the point a leading 0 (:919-923), so eq_row has a zero upper half and h
+ * is zero-padded to b for s only; f is never padded.  The caller's transcript has absorbed f, u and e (:905-907) before the call; `eval`
+ * is no argument (the prover uses it in debug assertions only).  Steps and callback stages (count and data as in nmx_transcript_fn_kzg):
+ *   1. eq_row, eq_col (:937-938); h (nmx_mercury_h_poly's pass, :966); commit h over n_rows coefficients (:987).  STAGE 0: 1 point,
+ *      comm_h -> alpha (:988-991)
+ *   2. q, g (nmx_mercury_divide_by_binomial's pass, :995); ONE fused batch commitment of q over (n_rows - 1) b coefficients and g over b
+ *      (:1046-1049).  STAGE 1: 2 points, comm_q then comm_g as the reference absorbs them (:1050-1051) -> gamma (:1068)
+ *   3. s = nmx_mercury_s_poly(eq_col, g, eq_row, h, gamma) (:1072-1077); d = g reversed (:1113-1120); ONE fused batch commitment of s over
+ *      b - 1 coefficients and d over b (:1123-1126).  STAGE 2: 2 points, comm_s then comm_d (:1128-1129) -> zeta (:1132)
+ *   4. zeta^-1 (:1134); [g, h, s, d] at [zeta, zeta^-1, alpha] in one nmx_poly_eval_multi launch, eight of the twelve values used
+ *      (:1136-1159).  STAGE 3: 6 scalars in the order of out_evals (the reference absorbs them under six labels, :1203-1208); what the
+ *      callback writes is ignored
+ *   5. quot_f (:1163-1180): the quotient pass over [f, q] with weight -(zeta^b - alpha) at the one point zeta (the k = 2, m = 1 case of
+ *      nmx_poly_lincomb_quotients, or lincomb_powers + suffix Horner, by the option kzg_fused_quotients); out[0] is compared with g(zeta)
+ *      (the reference's assert_eq!(rem, ZERO), :1177: a difference is a library bug, NMX_E_HIP); commit out[1..n) (:1212-1217).
+ *      STAGE 4: 1 point, comm_quot_f (:1218) -> beta (:586)
+ *   6. the batch opening (BDFG20 4.1, :567-770) on the host, O(b) products: the interpolants g*, h*, s*, d* in closed form (:592-614),
+ *      m(X) (:619-665), W = m / (X - alpha) / (X - zeta) / (X - 1/zeta) with every remainder checked (:668-674), b - 1 coefficients;
+ *      commit W (:677).  STAGE 5: 1 point, comm_w -> z (:678-682).  L(X) (:687-751), W' = L / (X - z), remainder checked (:754-761);
+ *      commit W' (:764).  STAGE 6: 1 point, comm_w_prime (:1249); what the callback writes is ignored (the reference squeezes the
+ *      pairing challenge d only to keep the transcripts aligned, :1250).  g, h and s are read back once (32 b bytes each), W and W' are
+ *      uploaded for their commitments.
+ * Mercury's verify, G2 and tau_H stay the caller's.
+ *   ck_handle   a registered key on ONE device with at least n points, of any of the four curves (the field is the curve's scalar
+ *               field); unknown, shorter than n or sharded over several devices: NMX_E_HANDLE
+ *   poly        n elements; host, or HBM with NMX_SCALARS_DEVICE; canonical, or Montgomery limbs with NMX_SCALARS_MONT (then the
+ *               challenges and the evaluations are Montgomery too).  Never modified.
+ *   point       host, ell elements, in the reference's order; an element >= p: NMX_E_SCALAR_RANGE
+ *   transcript  (ctx, stage, data, count, is_inf, out32) -> 0, or non-zero: NMX_E_ARG.  Points are affine canonical x || y of 64 bytes
+ *               (NMX_BASES_MONT: Montgomery limbs) with is_inf[i] = point i is the identity; scalars (stage 3) are 32 bytes each in the
+ *               scalars' form with is_inf = NULL.  A challenge written to out32 (stages 0, 1, 2, 4, 5) >= p: NMX_E_SCALAR_RANGE.
+ *               zeta = 0 (zeta.invert().unwrap(), :1134), zeta^2 = 1, alpha = zeta or alpha = 1/zeta: NMX_E_ZERO -- the interpolation
+ *               points coincide and the reference's elimination has no solution.  alpha = 0, gamma = 0, beta = 0 and any z (an
+ *               interpolation point included) are legal.  The callback runs on the calling thread and MUST NOT synchronise the device.
+ *   out_comms   8 points of 64 bytes in the order of the fields of EvaluationArgument: comm_h, comm_g, comm_q, comm_s, comm_d,
+ *               comm_quot_f, comm_w, comm_w_prime;   out_is_inf   their 8 identity bytes (may be NULL)
+ *   out_evals   6 scalars: g_zeta, g_zeta_inv, h_zeta, h_zeta_inv, s_zeta, s_zeta_inv
+ * Flags: NMX_SCALARS_MONT, NMX_SCALARS_DEVICE, NMX_ASYNC (accepted; the call is synchronous), NMX_BASES_MONT; anything else NMX_E_ARG.
+ * n not a power of two or n < 4, a NULL among poly, point, transcript, out_comms, out_evals: NMX_E_ARG; n >= 2^31: NMX_E_TOO_LARGE; all
+ * before a device or a key is touched.  On an error the outputs written so far are unspecified, nothing of the call still runs and the
+ * next call on the same key works.  Synchronous, ordered behind the calling thread's NMX_ASYNC calls; thread-safe like
+ * nmx_hyperkzg_prove; the workspace is the call's own (the context's aux buffer).  The zero polynomial gives eight identity points. */
+int nmx_mercury_prove(uint64_t ck_handle, const void* poly, size_t n, const void* point, uint32_t flags, nmx_transcript_fn_kzg transcript,
+                      void* ctx, uint8_t* out_comms /* 8 x 64 */, uint8_t* out_is_inf /* 8 or NULL */, uint8_t* out_evals /* 6 x 32 */);
 /* InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390), reached through EvaluationEngine::verify (:80-99) from
  * RelaxedR1CSSNARK::verify (src/spartan/snark.rs:384, ppsnark.rs:1645) inside CompressedSNARK::verify (src/nova/mod.rs:912), from the
  * point where the caller's transcript has produced its challenges: the verifier's transcript never waits for the device (it absorbs
@@ -891,6 +939,23 @@ int nmx_mercury_h_poly(int field_id, const void* f, size_t n_rows, size_t n_cols
  * of nmx_set_option sets the rows per segment (0 = by size) and never changes a result. */
 int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, size_t n_cols, const void* alpha,
                                    uint32_t flags, void* out_q /* (n_rows - 1) * n_cols */, void* out_g /* n_cols */);
+/* make_s_polynomial((a1, a2), (b1, b2), log_b, gamma) (mercury.rs:391-475, called at :1072-1077 with (eq_col, eq_row) and (g, h)): the
+ * coefficients of X^1 .. X^(b-1) of the Laurent polynomial a1(X) b1(1/X) + a1(1/X) b1(X) + gamma (a2(X) b2(1/X) + a2(1/X) b2(X)):
+ *   s[k] = sum_{i=0}^{b-2-k} ( a1[i+k+1] b1[i] + a1[i] b1[i+k+1] ) + gamma sum_{i=0}^{b-2-k} ( a2[i+k+1] b2[i] + a2[i] b2[i+k+1] ),  k < b - 1
+ * The reference multiplies by X^(b-1) and goes through four forward FFTs and one inverse FFT of size 2b; nothing wraps mod X^(2b) - 1, so
+ * what its drain(..b) keeps is this correlation.  It is exact field arithmetic, independent of any root of unity: valid in all four
+ * fields (Grumpkin's scalar field has 2-adicity 1 and no FFT of size 2b) and for ANY b >= 1, no power of two required.  b - 1 canonical
+ * elements are written, UNTRIMMED: the reference's trim() drops zero top coefficients, which change neither commit(ck, s) nor an
+ * evaluation; where the sum vanishes identically (f = 0) the reference's drain(..b) panics and this call writes zeros.  b == 1: the
+ * output is empty, out_s may be NULL and no device is needed.  Flags, words and buffers as for the two passes above: gamma is a host
+ * pointer in the vectors' form; every vector pointer follows NMX_SCALARS_DEVICE; NMX_ASYNC with HBM operands; operand words may be any
+ * 256-bit value, read mod p.  Errors, found before a device is touched, nothing written: a NULL pointer, a field_id that is none of
+ * NMX_F_*, b == 0, another flag, out_s overlapping an input: NMX_E_ARG; gamma >= p: NMX_E_SCALAR_RANGE; b > 2^16: NMX_E_TOO_LARGE (the
+ * prover's n stays below 2^31, so its b stays at or below 2^16; the work is 2 b^2 products).  The (k, i) triangle is cut into square
+ * tiles, one block each, partial sums exact and added by a finish; option "mercury_s_tile" of nmx_set_option sets the
+ * tile (0 = by size, 16, 32, 64) and never changes a byte. */
+int nmx_mercury_s_poly(int field_id, const void* a1, const void* b1, const void* a2, const void* b2, size_t b,
+                       const void* gamma, uint32_t flags, void* out_s /* b - 1 */);
 /* ---- NeutronNova's folding step (neutron::NIFS::prove, src/neutron/nifs.rs:200-289) ----------------------------------------------------
  * The N-sized work of neutron::NIFS::prove that no other call expresses; its commitments are nmx_commit / nmx_msm_u64 and its two
  * multiply_vec products nmx_spmv_apply_many.  Notation: for left, right >= 1, E is a vector of left + right elements,
@@ -1067,6 +1132,7 @@ int nmx_set_window_bits(uint32_t c);
  * round of the single-pass scan, 64; 1..63 force its multi-round path in tests), "horner_sub" (512-coefficient sub-tiles per
  * wave of the scan: 0 = by size, 1, 2, 4), "eq_max_blocks" (grid cap of the eq-factored sum passes: 0 = 768 for evaluate_with, 2048 otherwise), "horner_spin_limit" (polls before a wave of the scan gives up and the call falls back
  * to the two-pass kernels: 0 = 2^22; tests set 1),
+ * "mercury_s_tile" (outputs x indices per block of nmx_mercury_s_poly's kernel: 0 = by size, or 16, 32, 64; the same bytes at every value),
  * "mercury_seg_rows" (rows per segment of nmx_mercury_divide_by_binomial's kernels: 0 = by size; tests force the multi-segment path
  * at tiny shapes),
  * "neutron_max_blocks" (the largest grid of nmx_neutron_fold_sums / nmx_neutron_relation_sum: 0 = by size, at most 2048; tests force a

@@ -568,6 +568,48 @@ EvaluationArgument prove(const CommitmentKey& ck, const std::vector<Scalar>& hat
 }
 }  // namespace hyperkzg
 
+// Mercury's evaluation argument (src/provider/mercury.rs:891-1268) over the C ABI's one call.  `Transcript` is the caller's, of the shape
+// hyperkzg::prove takes: stage 0 absorbs comm_h and squeezes alpha, stage 1 comm_q and comm_g -> gamma, stage 2 comm_s and comm_d -> zeta,
+// stage 3 the six evaluations (count = 6 scalars; what it returns is ignored), stage 4 comm_quot_f -> beta, stage 5 comm_w -> z, stage 6
+// comm_w_prime (ignored: the reference squeezes the pairing challenge there).  The caller has absorbed f, u and e (:905-907) before.  It
+// runs on the calling thread and must not synchronise the device.  verify, G2 and tau_H stay the caller's.
+namespace mercury {
+using provider::check;
+using provider::CommitmentKey;
+using provider::Point;
+using provider::Scalar;
+
+struct EvaluationArgument {  // the fields of the reference's struct, in its order
+  Point comm_h, comm_g, comm_q, comm_s, comm_d, comm_quot_f, comm_w, comm_w_prime;
+  Scalar g_zeta{}, g_zeta_inv{}, h_zeta{}, h_zeta_inv{}, s_zeta{}, s_zeta_inv{};
+};
+namespace detail {
+// poly: n = 2^ell >= 4 elements where `flags` says; point: ell coordinates in the reference's order
+inline EvaluationArgument prove_call(const CommitmentKey& ck, const void* poly, size_t n, const std::vector<Scalar>& point, uint32_t flags,
+                                     nmx_transcript_fn_kzg cb, void* ctx) {
+  size_t ell = 0;
+  while (((size_t)1 << ell) < n) ell++;
+  if (n < 4 || point.size() != ell) throw std::invalid_argument("mercury::prove: n = 2^ell >= 4 and ell coordinates");
+  std::vector<uint8_t> comms(512), infs(8), evals(192);
+  check(nmx_mercury_prove(ck.handle(), poly, n, point.data(), flags | (ck.mont() ? NMX_BASES_MONT : 0u), cb, ctx, comms.data(), infs.data(),
+                          evals.data()));
+  EvaluationArgument out;
+  Point* const pts[8] = {&out.comm_h, &out.comm_g, &out.comm_q, &out.comm_s, &out.comm_d, &out.comm_quot_f, &out.comm_w, &out.comm_w_prime};
+  for (size_t i = 0; i < 8; i++) {
+    std::copy(comms.begin() + 64 * i, comms.begin() + 64 * i + 64, pts[i]->xy.begin());
+    pts[i]->is_inf = infs[i] != 0;
+  }
+  Scalar* const evs[6] = {&out.g_zeta, &out.g_zeta_inv, &out.h_zeta, &out.h_zeta_inv, &out.s_zeta, &out.s_zeta_inv};
+  for (size_t i = 0; i < 6; i++) std::copy(evals.begin() + 32 * i, evals.begin() + 32 * i + 32, evs[i]->begin());
+  return out;
+}
+}  // namespace detail
+template <class Transcript>
+EvaluationArgument prove(const CommitmentKey& ck, const std::vector<Scalar>& poly, const std::vector<Scalar>& point, Transcript& tr, bool mont = false) {
+  return detail::prove_call(ck, poly.data(), poly.size(), point, mont ? NMX_SCALARS_MONT : 0u, &hyperkzg::detail::stage_cb<Transcript>, &tr);
+}
+}  // namespace mercury
+
 // Hosts that keep their vectors in HBM between provider calls (INTEGRATION.md sections 2b-2e: the patched r1cs/mod.rs, nifs.rs,
 // snark.rs): the same operations over device pointers.  Thin by design -- each function is one C call with NMX_SCALARS_DEVICE (and
 // NMX_ASYNC where the host does not look at the result before its next synchronous call); allocation is the host's business
@@ -866,6 +908,16 @@ inline void lincomb_quotients(int field, const std::vector<const void*>& polys, 
 inline hyperkzg::EvaluationArgument hyperkzg_prove(const CommitmentKey& ck, const void* hat_P, size_t n, const std::vector<Scalar>& point,
                                                    nmx_transcript_fn_kzg cb, void* ctx, bool mont = false) {
   return hyperkzg::detail::prove_call(ck, hat_P, n, point, kDev | (mont ? NMX_SCALARS_MONT : 0u), cb, ctx);
+}
+// make_s_polynomial (mercury.rs:391-475) as a correlation over HBM-resident vectors of b elements each; out_s: b - 1
+inline void mercury_s_poly(int field, const void* a1, const void* b1, const void* a2, const void* b2, size_t b, const Scalar& gamma, void* out_s) {
+  check(nmx_mercury_s_poly(field, a1, b1, a2, b2, b, gamma.data(), kAsync, out_s));
+}
+// EvaluationEngineTrait::prove of Mercury (mercury.rs:891-1268) over an HBM-resident polynomial of n = 2^ell >= 4 elements; the callback runs on
+// the calling thread and must not synchronise the device
+inline mercury::EvaluationArgument mercury_prove(const CommitmentKey& ck, const void* poly, size_t n, const std::vector<Scalar>& point,
+                                                 nmx_transcript_fn_kzg cb, void* ctx, bool mont = false) {
+  return mercury::detail::prove_call(ck, poly, n, point, kDev | (mont ? NMX_SCALARS_MONT : 0u), cb, ctx);
 }
 // InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) over an HBM-resident b_vec of n elements
 inline bool ipa_verify(const CommitmentKey& ck, const Affine& ck_c, const provider::Point& comm_a, const Scalar& c, const void* b, size_t n,

@@ -112,6 +112,7 @@ def lib():
     L.nmx_poly_suffix_horner.argtypes = [i, vp, sz, vp, u32, vp]
     L.nmx_mercury_h_poly.argtypes = [i, vp, sz, sz, vp, u32, vp]
     L.nmx_mercury_divide_by_binomial.argtypes = [i, vp, sz, sz, vp, u32, vp, vp]
+    L.nmx_mercury_s_poly.argtypes = [i, vp, vp, vp, vp, sz, vp, u32, vp]
     L.nmx_pow_split_evals.argtypes = [i, vp, sz, sz, u32, vp]
     L.nmx_neutron_fold_sums.argtypes = [i, sz, sz, vp, vp, vp, vp, vp, vp, vp, vp, vp, u32, vp]
     L.nmx_neutron_relation_sum.argtypes = [i, sz, sz, vp, vp, vp, vp, u32, vp]
@@ -148,6 +149,7 @@ def lib():
     L.nmx_masked_eq_evals.argtypes = [i, vp, sz, sz, u32, vp]
     L.nmx_ipa_prove.argtypes = [u64, vp, vp, vp, sz, u32, IPA_TRANSCRIPT_FN, vp, vp, vp, vp, vp]
     L.nmx_hyperkzg_prove.argtypes = [u64, vp, sz, vp, u32, KZG_TRANSCRIPT_FN, vp, vp, vp, vp, vp, vp]
+    L.nmx_mercury_prove.argtypes = [u64, vp, sz, vp, u32, KZG_TRANSCRIPT_FN, vp, vp, vp, vp]
     L.nmx_poly_lincomb_quotients.argtypes = [i, vp, vp, sz, vp, vp, sz, u32, vp]
     L.nmx_ipa_verify.argtypes = [u64, vp, vp, i, vp, vp, sz, vp, vp, vp, vp, vp, u32, vp, vp, vp, vp]
     L.nmx_set_profiling.argtypes = [i]

@@ -5,6 +5,7 @@
 #include <atomic>
 #include <condition_variable>
 #include <functional>
+#include <future>
 #include <list>
 #include <thread>
 
@@ -1272,6 +1273,7 @@ static void check_svec_against_key(const SVec& v, const BaseSet& bs, size_t n) {
 }  // namespace nmx
 
 #include "keyfile.hpp"
+#include "mercury_host.hpp"  // the host-only algebra of nmx_mercury_prove's batch opening
 
 using namespace nmx;
 
@@ -2604,6 +2606,25 @@ int nmx_mercury_divide_by_binomial(int field_id, const void* f, size_t n_rows, s
   });
 }
 
+// make_s_polynomial (mercury_s.hpp; src/provider/mercury.rs:391-475) as a cross-correlation: no power of two is needed
+int nmx_mercury_s_poly(int field_id, const void* a1, const void* b1, const void* a2, const void* b2, size_t b, const void* gamma, uint32_t flags,
+                       void* out_s) {
+  return guarded([&] {
+    require((flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_ASYNC)) == 0, NMX_E_ARG,
+            "nmx_mercury_s_poly: only NMX_SCALARS_MONT, NMX_SCALARS_DEVICE and NMX_ASYNC apply");
+    with_field(field_id, [](auto) {});
+    require(b >= 1, NMX_E_ARG, "nmx_mercury_s_poly: b must be at least 1");
+    require(b <= kMercurySMaxB, NMX_E_TOO_LARGE, "nmx_mercury_s_poly: b must stay at or below 2^16 (the work is quadratic)");
+    require(a1 && b1 && a2 && b2 && gamma && (out_s || b == 1), NMX_E_ARG, "null argument");
+    for (const void* in : {a1, b1, a2, b2})
+      require(!elems_overlap(out_s, b - 1, in, b), NMX_E_ARG, "nmx_mercury_s_poly: out_s overlaps an input");
+    require_canonical(field_id, gamma, 1, "nmx_mercury_s_poly: gamma >= field modulus");
+    if (b == 1) return;  // an empty output: no device needed
+    CtxLease L;
+    fv_mercury_s_poly(*L.c, field_id, a1, b1, a2, b2, b, gamma, flags, out_s);
+  });
+}
+
 // ---- HyperKZG's batched multi-point quotients (hyperkzg.hpp; src/provider/hyperkzg.rs:1007-1072) ------------------------------------------
 // Everything that can be refused is refused before a device is leased: a refused call needs no device, launches nothing, writes nothing.
 int nmx_poly_lincomb_quotients(int field_id, const void* const* polys, const size_t* lens, size_t k, const void* q, const void* points, size_t m,
@@ -3538,6 +3559,179 @@ int nmx_hyperkzg_prove(uint64_t ck_handle, const void* hat_P, size_t n, const vo
   });
 }
 
+// EvaluationEngineTrait::prove of Mercury (src/provider/mercury.rs:891-1268 with generate_batch_evaluate_arg, :567-770) as one call.  f is
+// viewed as n_rows x b (b = 2^(ell' / 2), ell' = ell rounded up to even; n_rows = n / b): h and the division by X^b - alpha are the two
+// passes of mercury.hpp, s the correlation of mercury_s.hpp, quot_f the k = 2, m = 1 case of HyperKZG's quotient pass (or lincomb_powers +
+// suffix Horner, by kzg_fused_quotients), and the batch opening of the four b-sized polynomials is host algebra (mercury_host.hpp) between
+// two commitments.  Six commitment batches, seven callbacks.  The workspace lives in the context's aux buffer like nmx_hyperkzg_prove's.
+int nmx_mercury_prove(uint64_t ck_handle, const void* poly, size_t n, const void* point, uint32_t flags, nmx_transcript_fn_kzg transcript, void* ctx,
+                      uint8_t* out_comms, uint8_t* out_is_inf, uint8_t* out_evals) {
+  return guarded([&] {
+    require(transcript != nullptr, NMX_E_ARG, "null transcript callback");
+    require(poly && point && out_comms && out_evals, NMX_E_ARG, "null argument");
+    require(!(flags & ~(uint32_t)(NMX_SCALARS_MONT | NMX_SCALARS_DEVICE | NMX_ASYNC | NMX_BASES_MONT)), NMX_E_ARG, "unsupported flag");
+    require(n >= 4 && (n & (n - 1)) == 0, NMX_E_ARG, "n must be a power of two, at least 4");  // assert!(log_n > 1) (:914)
+    require(n < ((size_t)1 << 31), NMX_E_TOO_LARGE, "polynomial too long");
+    size_t ell = 0;
+    while (((size_t)1 << ell) < n) ell++;
+    ensure_init();
+    auto bs = lookup(ck_handle);
+    require(bs->parts.empty(), NMX_E_HANDLE, "nmx_mercury_prove: a key sharded over several devices is not supported");
+    require(n <= bs->n, NMX_E_HANDLE, "ck shorter than the polynomial");
+    const CurveOps& o = ops(bs->curve);
+    const int field = o.scalar_field;
+    require_canonical(field, point, ell, "nmx_mercury_prove: a coordinate of the point >= field modulus");
+    const bool dev = (flags & NMX_SCALARS_DEVICE) != 0, mont = (flags & NMX_SCALARS_MONT) != 0;
+    const uint32_t sflags = (flags & NMX_SCALARS_MONT) | NMX_SCALARS_DEVICE;
+    const uint32_t mflags = (flags & (NMX_SCALARS_MONT | NMX_BASES_MONT)) | NMX_SCALARS_DEVICE;
+    const uint32_t fused_opt = G.kzg_fused_quotients.load(std::memory_order_relaxed);
+    const bool fused = fused_opt == 1 || (fused_opt == 2 && n >= kKzgFusedMinN);
+    // the shape (:911-931): an odd ell gets a leading zero coordinate; f is not padded
+    const size_t log_b = (ell + 1) / 2, b = (size_t)1 << log_b, n_rows = n / b, nq = (n_rows - 1) * b;
+    std::vector<uint8_t> pt(32 * 2 * log_b, 0);
+    memcpy(pt.data() + 32 * (2 * log_b - ell), point, 32 * ell);
+    const uint8_t *u_row = pt.data(), *u_col = pt.data() + 32 * log_b;  // (:933-935)
+    CtxLease L;
+    Ctx& c = *L.c;
+    const size_t full = pad256(n * 32), small = pad256(b * 32);
+    CallScratch own(c, (dev ? 0 : full) + 2 * full + (fused ? 0 : full) + 8 * small + 256, kKzgAuxMax);
+    // host ends of this call's copies: they outlive the wait of the catch block
+    std::vector<uint8_t> hg(32 * b), hh(32 * b), hs(32 * b), wbytes(32 * (b - 1));  // the batch opening's g, h, s, read back once; W / W'
+    uint8_t rem[32];
+    try {
+      const uint32_t* f = (const uint32_t*)poly;
+      if (!dev) {
+        uint32_t* st = own.carve(full);
+        HIPCHK(hipMemcpyAsync(st, poly, n * 32, hipMemcpyHostToDevice, c.stream));
+        f = st;
+      }
+      uint32_t *q = own.carve(full), *quot = own.carve(full), *Bvec = fused ? nullptr : own.carve(full);
+      uint32_t *eq_row = own.carve(small), *eq_col = own.carve(small), *h = own.carve(small), *g = own.carve(small), *sp = own.carve(small),
+               *d = own.carve(small), *Wd = own.carve(small), *Wpd = own.carve(small);
+      uint8_t* comm[8];  // in the order of EvaluationArgument's fields
+      for (int i = 0; i < 8; i++) comm[i] = out_comms + 64 * i;
+      uint8_t infs[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+      enum { kH, kG, kQ, kS, kD, kQuotF, kW, kWPrime };
+      auto publish = [&](int i, const uint8_t* xy, uint8_t inf) {
+        memcpy(comm[i], xy, 64);
+        infs[i] = inf;
+        if (out_is_inf) out_is_inf[i] = inf;
+      };
+      auto squeeze = [&](int stage, const uint8_t* data, size_t count, const uint8_t* inf, uint8_t* out32, const char* range_msg) {
+        require(transcript(ctx, stage, data, count, inf, out32) == 0, NMX_E_ARG, "the transcript callback failed");
+        if (range_msg) require_canonical(field, out32, 1, range_msg);
+      };
+      auto commit2 = [&](const void* v0, size_t l0, const void* v1, size_t l1, uint8_t* xy, uint8_t* inf) {
+        const void* vs[2] = {v0, v1};
+        const size_t ls[2] = {l0, l1};
+        async_mark(c);  // the helper lanes of the batch are ordered behind the passes enqueued so far
+        batch_impl(*bs, 0, bs->n, vs, ls, v1 ? 2 : 1, mflags, xy, inf, c);
+      };
+      uint8_t alpha[32], gamma[32], zeta[32], zeta_inv[32], beta[32], z[32], ignored[32], xy[128], inf2[2];
+      // 1. eq_row, eq_col (:937-938); h over the n_rows rows that hold data, zero above (:966-970); comm_h; alpha (:987-991)
+      fv_eq_evals(c, field, u_row, (uint32_t)log_b, sflags, eq_row);
+      fv_eq_evals(c, field, u_col, (uint32_t)log_b, sflags, eq_col);
+      if (n_rows < b) HIPCHK(hipMemsetAsync(h + 8 * n_rows, 0, (b - n_rows) * 32, c.stream));
+      fv_mercury_h_poly(c, field, f, n_rows, b, eq_col, sflags | NMX_ASYNC, h);
+      inf2[0] = inf2[1] = 0;
+      commit2(h, n_rows, nullptr, 0, xy, inf2);
+      publish(kH, xy, inf2[0]);
+      squeeze(0, comm[kH], 1, infs + kH, alpha, "nmx_mercury_prove: the challenge alpha >= field modulus");
+      // 2. q, g (:995); one fused batch of both (:1046-1049); gamma (:1050-1051, :1068)
+      fv_mercury_divide_by_binomial(c, field, f, n_rows, b, alpha, sflags | NMX_ASYNC, q, g);
+      inf2[0] = inf2[1] = 0;
+      commit2(q, nq, g, b, xy, inf2);
+      publish(kQ, xy, inf2[0]), publish(kG, xy + 64, inf2[1]);
+      squeeze(1, xy, 2, inf2, gamma, "nmx_mercury_prove: the challenge gamma >= field modulus");
+      // 3. s (:1072-1077), d = g reversed (:1113-1120); one fused batch; zeta (:1128-1132)
+      fv_mercury_s_poly(c, field, eq_col, g, eq_row, h, b, gamma, sflags | NMX_ASYNC, sp);
+      fv_mercury_reverse(c, g, b, d);
+      HIPCHK(hipMemcpyAsync(hg.data(), g, 32 * b, hipMemcpyDeviceToHost, c.stream));
+      HIPCHK(hipMemcpyAsync(hh.data(), h, 32 * b, hipMemcpyDeviceToHost, c.stream));
+      HIPCHK(hipMemcpyAsync(hs.data(), sp, 32 * (b - 1), hipMemcpyDeviceToHost, c.stream));
+      inf2[0] = inf2[1] = 0;
+      commit2(sp, b - 1, d, b, xy, inf2);
+      publish(kS, xy, inf2[0]), publish(kD, xy + 64, inf2[1]);
+      squeeze(2, xy, 2, inf2, zeta, "nmx_mercury_prove: the challenge zeta >= field modulus");
+      // 4. zeta^-1 (:1134); [g, h, s, d] at [zeta, zeta^-1, alpha] in one launch, eight of the twelve values used (:1136-1159)
+      require(fv_ipa_invert(field, zeta, sflags, zeta_inv), NMX_E_ZERO, "nmx_mercury_prove: the challenge zeta is zero");
+      uint8_t pts3[96], ev[12 * 32], s_weight[32];
+      memcpy(pts3, zeta, 32), memcpy(pts3 + 32, zeta_inv, 32), memcpy(pts3 + 64, alpha, 32);
+      bool distinct = true;
+      with_field(field, [&](auto F) {
+        using H = HostFp4<decltype(F)::value>;
+        auto get = [&](const uint8_t* w) { return mont ? H::from_mont256(w) : H::from_canonical(w); };
+        MercuryOpening<decltype(F)::value> probe;
+        distinct = probe.set_points(get(zeta), get(alpha));
+        H zb = get(zeta);  // -(zeta^b - alpha): the weight of q in quot_f (:1164-1171)
+        for (size_t i = 0; i < log_b; i++) zb = zb * zb;
+        const H wq = get(alpha) - zb;
+        if (mont) wq.to_mont256(s_weight);
+        else wq.to_canonical(s_weight);
+      });
+      require(distinct, NMX_E_ZERO, "nmx_mercury_prove: the opening points zeta, 1/zeta and alpha are not distinct");
+      const void* epolys[4] = {g, h, sp, d};
+      const size_t elens[4] = {b, b, b - 1, b};
+      fv_eval_multi(c, field, epolys, elens, 4, pts3, 3, sflags, ev);
+      const int used[6] = {0, 1, 3, 4, 6, 7};  // g_zeta, g_zeta_inv, h_zeta, h_zeta_inv, s_zeta, s_zeta_inv
+      for (int i = 0; i < 6; i++) memcpy(out_evals + 32 * i, ev + 32 * used[i], 32);
+      squeeze(3, out_evals, 6, nullptr, ignored, nullptr);  // (:1203-1208) the caller absorbs them; nothing is squeezed here
+      // 5. quot_f = (f - (zeta^b - alpha) q - g(zeta)) / (X - zeta) (:1163-1180): out[0] is the value at zeta, which must be g(zeta).
+      // 6. the batch opening (:567-770): W, comm_w, z, W', comm_w_prime.  Everything of m(X) that does not depend on beta -- the copies of
+      // g, h, s, the interpolants, the four products and their divisions (mercury_host.hpp prepare: ~19 b host products) -- runs on a
+      // helper thread under quot_f's commitment; behind beta 3 b products are left, behind z 6 b.
+      with_field(field, [&](auto F) {
+        constexpr int FID = decltype(F)::value;
+        using H = HostFp4<FID>;
+        auto get = [&](const uint8_t* w) { return mont ? H::from_mont256(w) : H::from_canonical(w); };
+        MercuryOpening<FID> op;
+        op.set_points(get(zeta), get(alpha));
+        std::future<void> prep = std::async(std::launch::async, [&] {  // host arithmetic only: no HIP call on this thread
+          op.load(hg.data(), hh.data(), hs.data(), b, mont);
+          op.set_evals(get(ev), get(ev + 32), get(ev + 96), get(ev + 128), get(ev + 160), get(ev + 192), get(ev + 224), get(ev + 288));
+          op.prepare();
+        });  // (its destructor waits: an exception below never leaves the thread running on `op`)
+        const void* qpolys[2] = {f, q};
+        const size_t qlens[2] = {n, nq};
+        void* const qouts[1] = {quot};
+        if (fused) {
+          fv_lincomb_quotients(c, field, qpolys, qlens, 2, s_weight, zeta, 1, sflags, qouts, true);
+        } else {
+          fv_lincomb(c, field, qpolys, qlens, 2, s_weight, n, sflags, Bvec);
+          fv_suffix_horner(c, field, Bvec, n, zeta, sflags, quot);
+        }
+        HIPCHK(hipMemcpyAsync(rem, quot, 32, hipMemcpyDeviceToHost, c.stream));
+        inf2[0] = inf2[1] = 0;
+        commit2(quot + 8, n - 1, nullptr, 0, xy, inf2);
+        stream_wait(c.stream);
+        if (memcmp(rem, ev, 32) != 0) throw std::runtime_error("nmx_mercury_prove: quot_f's remainder is not g(zeta) (a library bug)");  // (:1177)
+        publish(kQuotF, xy, inf2[0]);
+        squeeze(4, comm[kQuotF], 1, infs + kQuotF, beta, "nmx_mercury_prove: the challenge beta >= field modulus");  // (:1218, :586)
+        prep.get();
+        if (!op.make_w(get(beta)) || op.W.size() != b - 1) throw std::runtime_error("nmx_mercury_prove: m(X) does not vanish on T (a library bug)");
+        MercuryOpening<FID>::store(op.W, mont, wbytes.data());
+        HIPCHK(hipMemcpyAsync(Wd, wbytes.data(), 32 * (b - 1), hipMemcpyHostToDevice, c.stream));
+        inf2[0] = inf2[1] = 0;
+        commit2(Wd, b - 1, nullptr, 0, xy, inf2);
+        publish(kW, xy, inf2[0]);
+        squeeze(5, comm[kW], 1, infs + kW, z, "nmx_mercury_prove: the challenge z >= field modulus");  // (:678-682)
+        typename MercuryOpening<FID>::Poly wp;
+        if (!op.make_w_prime(get(z), wp) || wp.size() != b - 1) throw std::runtime_error("nmx_mercury_prove: L(z) is not zero (a library bug)");
+        MercuryOpening<FID>::store(wp, mont, wbytes.data());
+        HIPCHK(hipMemcpyAsync(Wpd, wbytes.data(), 32 * (b - 1), hipMemcpyHostToDevice, c.stream));
+        inf2[0] = inf2[1] = 0;
+        commit2(Wpd, b - 1, nullptr, 0, xy, inf2);
+        publish(kWPrime, xy, inf2[0]);
+      });
+      // the last squeeze only keeps the transcripts aligned (:1249-1250)
+      squeeze(6, comm[kWPrime], 1, infs + kWPrime, ignored, nullptr);
+    } catch (...) {
+      (void)hipStreamSynchronize(c.stream);  // nothing of this call still reads the caller's polynomial or the workspace
+      throw;
+    }
+  });
+}
+
 // InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) as one call.  Every argument check comes first; then the challenges
 // are validated and turned into r^2, r^-2 and the kernel's constants on the host (ipa_verify.hpp), the O(log n) left side
 //   P_hat = sum r_k^2 L_k + sum r_k^-2 R_k + comm_a + c ck_c                                                   (:358-376)
@@ -3857,7 +4051,10 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "horner_window") G.horner_window = value ? value : 64u;
     else if (n == "horner_sub") G.horner_sub = value;
     else if (n == "mercury_seg_rows") G.mercury_seg_rows = value;
-    else if (n == "kzg_fused_quotients") {
+    else if (n == "mercury_s_tile") {
+      require(value == 0 || value == 16 || value == 32 || value == 64, NMX_E_ARG, "mercury_s_tile: 0 = by size, or 16, 32 or 64");
+      G.mercury_s_tile = value;
+    } else if (n == "kzg_fused_quotients") {
       require(value <= 2, NMX_E_ARG, "kzg_fused_quotients: 0 = lincomb_powers + 3 x suffix Horner, 1 = the fused pass, 2 = by size");
       G.kzg_fused_quotients = value;
     }

@@ -1731,6 +1731,7 @@ void fv_bind(Ctx& c, int field, const void* z, size_t z_len, size_t lo_off, size
 
 #include "r1cs_eval.hpp"
 #include "mercury.hpp"
+#include "mercury_s.hpp"
 #include "hyperkzg.hpp"
 #include "ppsnark_oracles.hpp"
 #include "ppsnark_key.hpp"

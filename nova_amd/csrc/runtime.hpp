@@ -340,6 +340,7 @@ struct Global {
   std::atomic<uint32_t> kzg_fused_quotients{2};   // option kzg_fused_quotients: nmx_hyperkzg_prove's three openings: 1 = ONE pass over the folded polynomials (hyperkzg.hpp), 0 = lincomb_powers + 3 x suffix Horner, 2 = by size (the pass from kKzgFusedMinN coefficients, capi.hip).  Same bytes either way
   std::atomic<uint32_t> kzg_quot_chunk{0};        // option kzg_quot_chunk: coefficients per lane of that pass's level 0 (0 / 4 = 4, 8 = 8)
   std::atomic<uint32_t> kzg_quot_scratch{1};      // option kzg_quot_scratch: 1 = the heads pass stores B and the walk reads it back, 0 = the walk sums it again
+  std::atomic<uint32_t> mercury_s_tile{0};       // option mercury_s_tile: outputs x indices per block of nmx_mercury_s_poly's kernel (mercury_s.hpp mercury_s_plan; 0 = by size, else 16, 32 or 64).  Same bytes at every value
   std::atomic<uint32_t> mercury_seg_rows{0};     // option mercury_seg_rows: rows per segment of Mercury's division kernels (mercury.hpp mercury_plan; 0 = by size; tests force the multi-segment path at tiny shapes)
   std::atomic<uint32_t> fixed_base_c{kFbDefaultC};         // option fixed_base_c: window width of the fixed-base key kernels (fixed_base.hpp; 4 .. 16, default 8: docs/measurements.md)
   std::atomic<uint32_t> derive_lmax{0};            // option derive_lmax: the longest run one lane of nmx_bases_derive_by_address adds (derive_key.hpp; 0 = derive_default_lmax, 2 .. 1024; tests reach the split and fold passes with few points)
@@ -907,6 +908,11 @@ void fv_r1cs_evaluate(Ctx&, int field, const CsrView* mats, size_t k, const void
 void fv_mercury_h_poly(Ctx&, int field, const void* f, size_t n_rows, size_t n_cols, const void* eq_col, uint32_t flags, void* out_h);
 void fv_mercury_divide_by_binomial(Ctx&, int field, const void* f, size_t n_rows, size_t n_cols, const void* alpha, uint32_t flags,
                                    void* out_q, void* out_g);
+// make_s_polynomial as a cross-correlation (mercury_s.hpp): b - 1 elements, b <= kMercurySMaxB; gamma is a host scalar in the vectors' form
+static constexpr size_t kMercurySMaxB = (size_t)1 << 16;  // the prover's n stays below 2^31, so its b stays at or below 2^16; the work is quadratic
+void fv_mercury_s_poly(Ctx&, int field, const void* a1, const void* b1, const void* a2, const void* b2, size_t b, const void* gamma, uint32_t flags,
+                       void* out_s);
+void fv_mercury_reverse(Ctx&, const uint32_t* in, size_t n, uint32_t* out);  // device vectors, enqueued: out[i] = in[n - 1 - i]
 // HyperKZG's batched multi-point quotients (hyperkzg.hpp): out_j[t] = sum_{s >= t} B[s] u_j^(s - t), B = sum_i q^i f_i, m <= 3 points.
 // Vectors follow NMX_SCALARS_DEVICE, q and the points are host pointers; NMX_ASYNC with HBM operands.  chain: a step of a longer call on
 // the same stream (nothing waited for, nothing marked).  Shapes, NULLs and overlaps are the caller's to check.

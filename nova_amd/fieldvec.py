@@ -483,6 +483,19 @@ def mercury_divide_by_binomial(field, f, n_rows, n_cols, alpha, mont=False, asyn
     return q, g
 
 
+def mercury_s_poly(field, a1, b1, a2, b2, gamma, mont=False, async_=False):
+    """make_s_polynomial((a1, a2), (b1, b2), log_b, gamma) (mercury.rs:391-475) without its FFTs (nmx_mercury_s_poly): the b - 1
+    coefficients of X^1 .. X^(b-1) of a1(X) b1(1/X) + a1(1/X) b1(X) + gamma (a2(X) b2(1/X) + a2(1/X) b2(X)), untrimmed, for four vectors
+    of any equal length b >= 1 (all host arrays or all CUDA tensors); gamma a host scalar."""
+    ps = [_vec(x) for x in (a1, b1, a2, b2)]
+    b, dev = ps[0][1], ps[0][2]
+    assert all(q[1] == b and q[2] == dev for q in ps), "four vectors of one length, all host or all HBM"
+    gg = _chal(gamma)
+    po, out = _out_like(dev, b - 1, a1)
+    _check(L.lib().nmx_mercury_s_poly(field, ps[0][0], ps[1][0], ps[2][0], ps[3][0], b, gg.ctypes.data, _flags(dev, mont, async_), po if b > 1 else None))
+    return out
+
+
 def mercury_quot_f(field, f, q, zeta_b_minus_alpha, zeta, mont=False):
     """The quot_f block (mercury.rs:1163-1180) from calls that exist: f - (zeta^b - alpha) q through lincomb_powers over [f, q] with
     s = -(zeta^b - alpha), then suffix_horner at zeta -> (quot, rem).  quot = out[1:] is (f - (zeta^b - alpha) q - g(zeta)) / (X - zeta): it

@@ -650,6 +650,51 @@ def hyperkzg_prove(ck, hat_P, point, transcript, ctx=None, mont=False):
             [(wb[64 * j: 64 * j + 64], bool(owi[j])) for j in range(3)])
 
 
+def as_mercury_transcript(fn):
+    """fn(stage: int, data: bytes, count: int, is_inf: bytes or None) -> 32-byte challenge (ignored at stages 3 and 6), wrapped as
+    nmx_transcript_fn_kzg for nmx_mercury_prove.  Stage 0: comm_h -> alpha; 1: comm_q, comm_g -> gamma; 2: comm_s, comm_d -> zeta; 3: the six
+    evaluations (count = 6 scalars of 32 bytes, is_inf None); 4: comm_quot_f -> beta; 5: comm_w -> z; 6: comm_w_prime.  Points are 64 bytes
+    each.  The callback runs on the calling thread and must not synchronise the device."""
+    if isinstance(fn, L.KZG_TRANSCRIPT_FN):
+        return fn
+
+    def cb(_ctx, stage, data, count, is_inf, out):
+        try:
+            size = (32 if stage == 3 else 64) * count
+            ch = fn(int(stage), bytes(data[:size]), int(count), bytes(is_inf[:count]) if is_inf else None)
+            if ch is not None:
+                ctypes.memmove(out, ch, 32)
+            return 0
+        except Exception:                   # an exception must not cross the C frame: the call fails with NMX_E_ARG
+            import traceback
+            traceback.print_exc()
+            return 1
+    return L.KZG_TRANSCRIPT_FN(cb)
+
+
+MERCURY_COMMS = ("comm_h", "comm_g", "comm_q", "comm_s", "comm_d", "comm_quot_f", "comm_w", "comm_w_prime")
+MERCURY_EVALS = ("g_zeta", "g_zeta_inv", "h_zeta", "h_zeta_inv", "s_zeta", "s_zeta_inv")
+
+
+def mercury_prove(ck, poly, point, transcript, ctx=None, mont=False):
+    """EvaluationEngineTrait::prove of Mercury (src/provider/mercury.rs:891-1268) as one call (nmx_mercury_prove): `ck` a CommitmentKey on
+    one device with at least len(poly) points, poly the 2^ell >= 4 evaluations (a host array or a CUDA tensor, never modified), point the
+    ell coordinates (host, in the reference's order), transcript a callable for as_mercury_transcript or a KZG_TRANSCRIPT_FN (with ctx);
+    the caller's transcript has absorbed f, u and e before.  The callback runs on the calling thread and must not synchronise the device.
+    Returns (comms, evals): comms = [(xy64, is_identity)] * 8 in the order of MERCURY_COMMS, evals = six 32-byte scalars in the order of
+    MERCURY_EVALS.  verify and the pairing stay the caller's."""
+    pp, n, dev, _kp = _scalar_arg(poly, 32)
+    ell = max(n.bit_length() - 1, 0)
+    pt = _host_u8(point, 32)
+    assert pt.size == 32 * ell, "point has log2(len(poly)) coordinates"
+    oc, oi, oe = np.zeros(512, np.uint8), np.zeros(8, np.uint8), np.zeros(192, np.uint8)
+    flags = dev | (L.SCALARS_MONT if mont else 0) | (L.BASES_MONT if ck.mont else 0)
+    cb = as_mercury_transcript(transcript)
+    _check(L.lib().nmx_mercury_prove(ck.handle, pp, n, pt.ctypes.data if ell else None, flags, cb, ctx, oc.ctypes.data, oi.ctypes.data, oe.ctypes.data))
+    cb_, eb = oc.tobytes(), oe.tobytes()
+    return [(cb_[64 * j: 64 * j + 64], bool(oi[j])) for j in range(8)], [eb[32 * j: 32 * j + 32] for j in range(6)]
+
+
 def ipa_verify(ck, ck_c_xy64, comm_a, c, b, L_vec, R_vec, infs, a_hat, rs, mont=False, point=False, want_intermediates=False):
     """InnerProductArgument::verify (src/provider/ipa_pc.rs:286-390) over a registered Pedersen key, from the point where the caller's
     transcript has produced the round challenges `rs` (32 bytes each, round 0 first).  `comm_a`: a Commitment, (xy64, is_inf) or 64

@@ -151,6 +151,11 @@ def generate():
           "/// One stage of HyperKZG's evaluation argument (nmx_hyperkzg_prove): stage 0 absorbs `count` commitments of 64 bytes (`is_inf[i]`: point i is the",
           "/// identity) and squeezes r, stage 1 absorbs `count` scalars of 32 bytes (`is_inf` null) and squeezes q, stage 2 absorbs the three w.  It must not",
           "/// synchronise the device.",
+          "/// The same type serves Mercury's evaluation argument (nmx_mercury_prove), whose stages are:",
+          "///   stage 0: 1 point  (comm_h)              -> alpha        stage 1: 2 points (comm_q, comm_g)  -> gamma",
+          "///   stage 2: 2 points (comm_s, comm_d)      -> zeta         stage 3: 6 scalars (g_zeta, g_zeta_inv, h_zeta, h_zeta_inv, s_zeta, s_zeta_inv), output ignored",
+          "///   stage 4: 1 point  (comm_quot_f)         -> beta         stage 5: 1 point  (comm_w)          -> z",
+          "///   stage 6: 1 point  (comm_w_prime), output ignored (the reference squeezes the pairing challenge d here).",
           "pub type NmxTranscriptFnKzg = unsafe extern \"C\" fn(ctx: *mut c_void, stage: c_int, data: *const u8, count: usize, is_inf: *const u8,",
           "                                                     out32: *mut u8) -> c_int;",
           "",
