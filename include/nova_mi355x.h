@@ -1157,6 +1157,9 @@ int nmx_set_window_bits(uint32_t c);
  * "accum_prio" (progress-keyed wave priority in the segment accumulate: 0 = by rule, 1 = off, 2 = on -- a wave starts at priority 3 and
  * steps down after a half, three quarters and seven eighths of its segment --, 3 = on with steps after equal quarters; other values:
  * NMX_E_ARG; ignored where the segment accumulate does not run),
+ * "part_rows" (first level of the bucket partition: 0 = by rule, 1 = counting and placing passes that reserve runs with global atomics,
+ * 2 = per-chunk count rows and a column scan, no global atomics, wherever the shape allows -- window tables of width 15, 16 or 17, keys
+ * of up to 16 bits, more than one first-level bin; other values: NMX_E_ARG; same bytes either way),
  * "hist_grid" (blocks of the partition's counting pass; 0 = as the placing pass: measured flat, profiles/r03_msm_2p20/tail_ab.txt),
  * "shard_min_n", "cache_table_after", "max_table_mib" (see the sections above), "force_peer_copy" (1: the HBM-resident scalars of
  * a sharded call are staged through hipMemcpyPeerAsync even when the shard sits on the source GPU: exercises the cross-device

@@ -201,6 +201,11 @@ static void ensure_init() {
     require(v >= 0 && v <= 3, NMX_E_ARG, "NMX_TUNE_ACCUM_PRIO: 0 = by rule, 1 = off, 2 = on, 3 = on with equal quarters");
     G.accum_prio = (uint32_t)v;
   }
+  if (const char* t = getenv("NMX_TUNE_PART_ROWS")) {
+    const int v = atoi(t);
+    require(v >= 0 && v <= 2, NMX_E_ARG, "NMX_TUNE_PART_ROWS: 0 = by rule, 1 = level 1 with global atomics, 2 = count rows wherever the shape allows");
+    G.part_rows = (uint32_t)v;
+  }
   HIPCHK(hipSetDevice(dev));
   cache_init_defaults();
   if (const char* t = getenv("NMX_DEVICES")) {  // same as nmx_init_devices(k, 0), for hosts that cannot call it
@@ -4005,6 +4010,10 @@ int nmx_set_option(const char* name, uint32_t value) {
     else if (n == "accum_prio") {
       require(value <= 3, NMX_E_ARG, "accum_prio: 0 = by rule, 1 = off, 2 = on, 3 = on with equal quarters");
       G.accum_prio = value;
+    }
+    else if (n == "part_rows") {
+      require(value <= 2, NMX_E_ARG, "part_rows: 0 = by rule, 1 = level 1 with global atomics, 2 = count rows wherever the shape allows");
+      G.part_rows = value;
     }
     else if (n == "no_batch_fuse") G.no_batch_fuse = value;
     else if (n == "prefix_tables") G.prefix_tables = value > 2 ? 2u : (uint32_t)value;

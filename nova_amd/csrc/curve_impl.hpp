@@ -108,7 +108,7 @@ static inline uint64_t shape_hash(const MsmArgs& a, const MsmCall& mc, size_t sb
   const uint64_t v[11] = {((uint64_t)cid << 56) | ((uint64_t)sbits << 40) | seg_lanes, a.n, a.u64_bits | ((uint64_t)((G.no_tree_fuse.load(std::memory_order_relaxed) & 15u) | (G.reduce_form.load(std::memory_order_relaxed) << 4) | (G.host_combine.load(std::memory_order_relaxed) << 6)) << 32) | ((uint64_t)G.tree_threads.load(std::memory_order_relaxed) << 40) | ((uint64_t)a.big_slice << 44), a.force_c, a.force_lmax, a.force_fold_t, ((uint64_t)a.pre_stride << 8) | a.pre_c,
                           (uint64_t)(mc.gather_host != nullptr) | (mc.all_ones ? 2u : 0u) | (mc.scalars_device ? 4u : 0u) |
                               (a.no_partition ? 8u : 0u),
-                          sbytes, a.seg_min_total, G.seg_lanes_override ^ ((uint64_t)a.seg_heavy_above << 32) ^ ((uint64_t)a.accum_prio << 40)};
+                          sbytes, a.seg_min_total, G.seg_lanes_override ^ ((uint64_t)a.seg_heavy_above << 32) ^ ((uint64_t)a.accum_prio << 40) ^ ((uint64_t)a.part_rows << 52)};
   uint64_t h = 0x9e3779b97f4a7c15ull;
   for (uint64_t x : v) {
     h = (h ^ x) * 0xff51afd7ed558ccdull;
@@ -146,6 +146,7 @@ static XYZZ<CurveT<CID>::BF> run_msm(Ctx& c, const void* d_bases, size_t n, cons
   a.big_slice = G.big_slice.load(std::memory_order_relaxed);
   a.hist_grid = G.hist_grid;
   a.hist_bs = G.hist_bs;
+  a.part_rows = part_rows_on(a.n);
   a.accum_clean = G.no_clean_accum.load(std::memory_order_relaxed) ? 0u : 1u;
   a.accum_prio = accum_prio_sched((size_t)a.n * 16);  // the estimate seg_lanes() is asked with below
 #if defined(NMX_ACCUM_TRACE)
@@ -427,6 +428,7 @@ static void run_msm_batch(Ctx& c, const BaseSet& bs, size_t offset, const BatchI
   a.big_slice = G.big_slice.load(std::memory_order_relaxed);
   a.hist_grid = G.hist_grid;
   a.hist_bs = G.hist_bs;
+  a.part_rows = part_rows_on(a.n);
   a.accum_clean = G.no_clean_accum.load(std::memory_order_relaxed) ? 0u : 1u;
   a.accum_prio = accum_prio_sched((size_t)a.n * 16);  // the estimate seg_lanes() is asked with below
 #if defined(NMX_ACCUM_TRACE)

@@ -225,6 +225,10 @@ struct PartBufs {
   // what the placing pass's cursor ends at.  The pipeline then runs k_part_hi FIRST (reporting range errors itself), k_tiles reads
   // the count from cur_hi, and k_hist_hi is not launched at all: one dependent launch less on MSMs that are pure latency.
   uint32_t single_bin = 0;
+  // count rows (k_count_rows / k_scan_rows / k_place_rows): per chunk q = scalars [q * bs1, (q + 1) * bs1) and high bin
+  uint16_t* row_cnt = nullptr;  // [chunks x nhi] entries of chunk q in the bin (<= bs1 * W <= 12288); every row is written
+  uint32_t* row_rel = nullptr;  // [chunks x nhi] entries of the chunks before q in the bin: chunk q's run starts there in the bin's region
+  uint32_t row_chunks = 0;      // ceil(n / bs1): rows are indexed by chunk, never by block (the grid strides over chunks)
 };
 template <int SFID> struct PartArgs {
   DigitSrc<SFID> src;
@@ -425,6 +429,132 @@ template <int SFID, int C, bool BIG> NMX_KERNEL void NMX_LAUNCH_BOUNDS(1024) k_p
         for_each_digit<SFID, C>(a.src, s, [&](uint32_t w, uint32_t d, uint32_t neg) { place(w, a.src.key_base(w, kbase) + d - 1, neg); });
       }
     }
+    NMX_SYNC();
+    const uint32_t tot = lbase[nhi];
+    for (uint32_t sl = t; sl < tot; sl += bs) {  // consecutive threads -> consecutive addresses inside a bin's run
+      const uint32_t key = stage_key[sl], bin = key >> LB;
+      const uint32_t g = gbase[bin] + (sl - lbase[bin]);
+      a.b.ent_val[g] = stage_val[sl];
+      ent_lo[g] = (LoT)(key & lomask);
+    }
+    NMX_SYNC();
+  }
+}
+
+// ----------------------------------------------------------------------------------------------------
+// level 1 with count rows (table mode, narrow geometry, more than one high bin, compile-time width; option part_rows)
+//
+// k_hist_hi ends with one global atomic per block and bin and k_part_hi reserves every chunk's runs with one RETURNING
+// device-scope atomic per bin -- ~350 k of them at 2^20 pairs on the same 256 addresses, ~1400 in a row per address, each
+// block waiting for its own -- after counting the chunk's digits a second time.  Here the counting pass keeps what it
+// counted: one row of bin counts per chunk.  A scan down the columns turns the rows into each chunk's offset inside the
+// bin's region, and the placing pass reads its row instead of counting and reserving: no global atomics at level 1, one LDS
+// atomic per entry and pass.  The bin regions are as packed as before (a chunk's run follows the runs of the chunks before
+// it); only the order inside a bin differs, which level 2 and the bucket sums do not see.
+//
+//   k_count_rows   chunk q -> LDS histogram of the high key bits -> row_cnt[q][.]   (every row written, empty chunks too)
+//   k_scan_rows    row_rel[q][bin] = sum of row_cnt[q'][bin] over q' < q; hist_hi[bin] = the column's total (k_tiles as before)
+//   k_place_rows   chunk q: lbase = block scan of its row, gbase = ent_base + row_rel[q][.], digits placed as they are extracted
+// ----------------------------------------------------------------------------------------------------
+static constexpr uint32_t kScanRows = 32, kScanBins = 32;  // k_scan_rows: 1024 threads, one per (chunk, bin) of a 32 x 32 tile
+inline uint32_t part_row_chunks(uint32_t n, uint32_t bs1) { return (n + bs1 - 1) / bs1; }
+inline uint32_t scan_rows_grid(uint32_t chunks, uint32_t nhi) {
+  return ((chunks + kScanRows - 1) / kScanRows) * ((nhi + kScanBins - 1) / kScanBins);
+}
+// the shapes the rows cover; every other shape keeps k_hist_hi / k_part_hi
+inline bool part_rows_supported(const MsmShape& sh, const PartShape& ps, bool table_mode) {
+  return table_mode && !ps.big && ps.nhi > 1 && (sh.c == 15 || sh.c == 16 || sh.c == 17);
+}
+
+// Launched with ps.bs1 threads, as the placing pass: both must cut the same chunks.
+template <int SFID, int C> NMX_KERNEL void NMX_LAUNCH_BOUNDS(1024) k_count_rows(PartArgs<SFID> a) {
+  using Cfg = PartCfg<false>;
+  NMX_LDS uint32_t cnt[Cfg::kMaxHi];
+  const uint32_t t = NMX_TID, bs = NMX_BDIM, LB = a.b.ps.LB, nhi = a.b.ps.nhi, n = a.src.sh.n;
+  for (uint32_t j = t; j < Cfg::kMaxHi; j += bs) cnt[j] = 0;
+  NMX_SYNC();
+  for (uint32_t q = NMX_BID; q < a.b.row_chunks; q += NMX_GDIM) {
+    const uint32_t i = q * bs + t;
+    if (i < n) {
+      uint32_t s[9], bi, kbase;
+      if (a.src.load(i, s, bi, kbase, true))
+        for_each_digit<SFID, C>(a.src, s, [&](uint32_t w, uint32_t d, uint32_t) { lds_count(cnt, (a.src.key_base(w, kbase) + d - 1) >> LB); });
+    }
+    NMX_SYNC();
+    for (uint32_t j = t; j < nhi; j += bs) {  // the row, and the counters cleared for the next chunk
+      a.b.row_cnt[(size_t)q * nhi + j] = (uint16_t)cnt[j];
+      cnt[j] = 0;
+    }
+    NMX_SYNC();
+  }
+}
+
+// Column scan, parallel over bins and over chunk ranges: block (range, group) owns chunks [32 * range, +32) x bins [32 * group, +32),
+// one thread per element.  A column's sum over the chunks before the range is taken by the block itself, 32 threads per column
+// (the whole matrix is <= 0.7 MB at 2^20 pairs and stays in cache: the re-reads cost less than a second launch for range totals,
+// and no block ever waits for another).  The block of the last chunk leaves the column totals in hist_hi.
+template <bool BIG> NMX_KERNEL void NMX_LAUNCH_BOUNDS(1024) k_scan_rows(PartBufs b) {
+  static_assert(!BIG, "count rows: narrow geometry only");
+  NMX_LDS uint32_t part[kScanRows][kScanBins], tile[kScanRows][kScanBins], base[kScanBins];
+  const uint32_t t = NMX_TID, nhi = b.ps.nhi, chunks = b.row_chunks;
+  const uint32_t groups = (nhi + kScanBins - 1) / kScanBins;
+  const uint32_t q0 = (NMX_BID / groups) * kScanRows, lb = t % kScanBins, r = t / kScanBins;  // blockDim = 1024: r < kScanRows
+  const uint32_t bin = (NMX_BID % groups) * kScanBins + lb;
+  const bool col = bin < nhi;
+  uint32_t before = 0;
+  if (col) {
+#pragma unroll 4
+    for (uint32_t q = r; q < q0; q += kScanRows) before += b.row_cnt[(size_t)q * nhi + bin];
+  }
+  const uint32_t q = q0 + r;
+  const bool mine = col && q < chunks;
+  const uint32_t own = mine ? b.row_cnt[(size_t)q * nhi + bin] : 0u;
+  part[r][lb] = before;
+  tile[r][lb] = own;
+  NMX_SYNC();
+  if (t < kScanBins) {
+    uint32_t s = 0;
+    for (uint32_t k = 0; k < kScanRows; k++) s += part[k][t];
+    base[t] = s;
+  }
+  NMX_SYNC();
+  uint32_t rel = base[lb];
+  for (uint32_t k = 0; k < r; k++) rel += tile[k][lb];
+  if (mine) {
+    b.row_rel[(size_t)q * nhi + bin] = rel;
+    if (q + 1 == chunks) b.hist_hi[bin] = rel + own;
+  }
+}
+
+template <int SFID, int C> NMX_KERNEL void NMX_LAUNCH_BOUNDS(1024) k_place_rows(PartArgs<SFID> a) {
+  using Cfg = PartCfg<false>;
+  using KeyT = typename Cfg::KeyT;
+  using LoT = typename Cfg::LoT;
+  NMX_LDS uint32_t stage_val[Cfg::kStage];
+  NMX_LDS KeyT stage_key[Cfg::kStage];
+  NMX_LDS uint32_t cnt[Cfg::kMaxHi], lbase[Cfg::kMaxHi + 1], gbase[Cfg::kMaxHi], cur[Cfg::kMaxHi], wtot[16];
+  const uint32_t t = NMX_TID, bs = NMX_BDIM;
+  const uint32_t n = a.src.sh.n, nhi = a.b.ps.nhi, LB = a.b.ps.LB, lomask = a.b.ps.nlo - 1u;
+  LoT* ent_lo = static_cast<LoT*>(a.b.ent_lo);
+  for (uint32_t q = NMX_BID; q < a.b.row_chunks; q += NMX_GDIM) {
+    const uint32_t i = q * bs + t;
+    uint32_t s[9], bi = 0, kbase = 0;
+    const bool live = i < n && a.src.load(i, s, bi, kbase, false);  // (range errors: the counting pass reported them)
+    for (uint32_t j = t; j < Cfg::kMaxHi; j += bs) {
+      cur[j] = 0;
+      cnt[j] = j < nhi ? a.b.row_cnt[(size_t)q * nhi + j] : 0u;
+      if (j < nhi) gbase[j] = a.b.tab[j] + a.b.row_rel[(size_t)q * nhi + j];  // the chunk's run in the bin's region
+    }
+    NMX_SYNC();
+    block_excl_scan(cnt, lbase, nhi, wtot);
+    // placed as extracted: LDS slot = bin's local base + arrival rank
+    if (live)
+      for_each_digit<SFID, C>(a.src, s, [&](uint32_t w, uint32_t d, uint32_t neg) {
+        const uint32_t key = a.src.key_base(w, kbase) + d - 1, bin = key >> LB;
+        const uint32_t slot = lbase[bin] + lds_rank(cur, bin);
+        stage_val[slot] = (w * a.src.pre_stride + bi) | (neg << 31);
+        stage_key[slot] = (KeyT)key;
+      });
     NMX_SYNC();
     const uint32_t tot = lbase[nhi];
     for (uint32_t sl = t; sl < tot; sl += bs) {  // consecutive threads -> consecutive addresses inside a bin's run

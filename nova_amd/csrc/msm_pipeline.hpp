@@ -47,6 +47,7 @@ struct MsmArgs {
   uint32_t batch_k = 0;
   const uint32_t* batch_off = nullptr;
   const uint32_t* const* batch_vec = nullptr;
+  uint32_t part_rows = 0;             // 1: level 1 of the partition keeps per-chunk count rows where the shape allows (msm_partition.hpp part_rows_supported; option part_rows)
 };
 
 inline uint32_t ilog2_u32(uint32_t v) {
@@ -225,6 +226,23 @@ MsmShape msm_pipeline(BE& be, const MsmArgs& a, uint32_t scalar_bits, XYZZW* wsu
     pb.total_out = counters + 5;
     // the widths the tables are built with get their own instantiation (constant bit positions); BIG = keys wider than 15 bits
     pb.single_bin = pb.ps.nhi == 1 ? 1u : 0u;
+    // count rows (k_count_rows / k_scan_rows / k_place_rows): no global atomics at level 1, every digit counted once per pass
+    const bool rows = a.part_rows && part_rows_supported(sh, pb.ps, a.pre_stride != 0);
+    if (rows) {
+      pb.row_chunks = part_row_chunks(sh.n, pb.ps.bs1);
+      pb.row_cnt = be.template alloc<uint16_t>((size_t)pb.row_chunks * pb.ps.nhi);
+      pb.row_rel = be.template alloc<uint32_t>((size_t)pb.row_chunks * pb.ps.nhi);
+    }
+    auto level1_rows = [&](auto count, auto place) {
+      be.mark("digits");
+      // (hist_bs does not apply: both passes cut the same chunks of bs1 scalars)
+      const uint32_t cgrid = a.hist_grid && a.hist_grid < pb.ps.grid1 ? a.hist_grid : pb.ps.grid1;
+      be.launch_kernel(count, cgrid, pb.ps.bs1, pa);
+      be.launch_kernel(&k_scan_rows<false>, scan_rows_grid(pb.row_chunks, pb.ps.nhi), 1024u, pb);
+      be.launch_kernel(&k_tiles<false>, 1u, 1024u, pb);
+      be.mark("sort");
+      be.launch_kernel(place, pb.ps.grid1, pb.ps.bs1, pa);
+    };
     auto level1 = [&](auto hist, auto part) {
       if (pb.single_bin) {  // (PartBufs::single_bin) placing pass first, the tile table from its cursor, no counting pass
         be.mark("digits");
@@ -261,6 +279,14 @@ MsmShape msm_pipeline(BE& be, const MsmArgs& a, uint32_t scalar_bits, XYZZW* wsu
       else level1(&k_hist_hi<SFID, 0, true>, &k_part_hi<SFID, 0, true>);
       be.launch_kernel(&k_hist_lo<true>, pb.ps.tiles_cap, kTileThreads, pb);
       be.launch_kernel(&k_part_lo<true>, pb.ps.tiles_cap, kTileThreads, pb);
+    } else if (rows) {
+      switch (sh.c) {  // (part_rows_supported: 15, 16 or 17)
+        case 17: level1_rows(&k_count_rows<SFID, 17>, &k_place_rows<SFID, 17>); break;
+        case 16: level1_rows(&k_count_rows<SFID, 16>, &k_place_rows<SFID, 16>); break;
+        default: level1_rows(&k_count_rows<SFID, 15>, &k_place_rows<SFID, 15>);
+      }
+      be.launch_kernel(&k_hist_lo<false>, pb.ps.tiles_cap, kTileThreads, pb);
+      be.launch_kernel(&k_part_lo<false>, pb.ps.tiles_cap, kTileThreads, pb);
     } else {
       switch (sh.c) {
         case 17: level1(&k_hist_hi<SFID, 17, false>, &k_part_hi<SFID, 17, false>); break;

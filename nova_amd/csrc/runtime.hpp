@@ -135,6 +135,7 @@ using BaseRef = std::shared_ptr<const BaseSet>;
 // everything but the trivial sizes.  (4096 until the small sizes were measured, scripts/gpu_smallmsm.py: with tables a
 // 2^11-pair MSM takes 0.29 ms instead of 0.98 -- one bucket set instead of 37, no 250-doubling Horner on the host.)
 static constexpr size_t kPrecompMinN = 2;  // default of Global::precomp_min_n
+static constexpr size_t kPartRowsMinN = (size_t)1 << 18;  // option part_rows = 0: count rows from this many pairs on (part_rows_on)
 // internal upload flag (never part of the ABI): the source array is a resident key already in the internal form -- no
 // ---------------------------------------------------------------------------------------------------
 // Helper threads: the shards of a multi-device call, the lanes of a batch, the host-side work that runs under a GPU MSM (the
@@ -357,7 +358,8 @@ struct Global {
   std::atomic<uint32_t> host_combine{0};          // env NMX_TUNE_HOST_COMBINE / option host_combine: the end of the bit-sliced reduction, root + sum_l 2^l O_l: 0 = by rule (DeviceBackend::reduce_bitsliced), 1 = on the device (the last launch combines), 2 = on the host wherever the slices fit the landing buffer (host_point4.hpp combine_slices)
   std::atomic<uint32_t> hist_grid{0};            // env NMX_TUNE_HIST_GRID / option hist_grid
   std::atomic<uint32_t> hist_bs{0};               // env NMX_TUNE_HIST_BS / option hist_bs: threads per block of k_hist_hi (0: as k_part_hi)
-  std::atomic<uint32_t> horner_order{1};          // option horner_order: 1 = tiles of k_horner_scan by start-order ticket, 0 = by block id
+  std::atomic<uint32_t> part_rows{0};             // env NMX_TUNE_PART_ROWS / option part_rows: level 1 of the partition with per-chunk count rows (msm_partition.hpp k_count_rows / k_scan_rows / k_place_rows): 0 = by rule (part_rows_on), 1 = the kernels with global atomics (k_hist_hi / k_part_hi), 2 = rows wherever the shape allows
+  std::atomic<uint32_t> horner_order{1};         // option horner_order: 1 = tiles of k_horner_scan by start-order ticket, 0 = by block id
   std::atomic<uint32_t> host_split{255};           // option host_split: a call with HOST scalars over >= host_split_min_n pairs of a single-device key is cut into this many pieces whose uploads overlap the previous piece's MSM (0 / 1: off)
   std::atomic<size_t> host_split_min_n{(size_t)1 << 19};
   std::atomic<uint32_t> sc_fused_sum{1};          // option sc_fused_sum: 1 = a sum-check round is ONE launch (the last block sums the partials, k_sc_pass); 0 = pass + final-sum launch
@@ -389,6 +391,11 @@ extern Global& G;                // capi.hip (heap singleton, never destroyed)
 static inline uint32_t accum_prio_sched(size_t total_entries) {
   const uint32_t v = G.accum_prio.load(std::memory_order_relaxed);
   return v == 1 ? 0u : v == 2 ? 0x764u : v == 3 ? 0x642u : total_entries >= ((size_t)1 << 21) ? 0x764u : 0u;
+}
+// option part_rows -> MsmArgs::part_rows (the pipeline still asks part_rows_supported for the shape).
+static inline uint32_t part_rows_on(size_t n) {
+  const uint32_t v = G.part_rows.load(std::memory_order_relaxed);
+  return v == 1 ? 0u : v == 2 ? 1u : n >= kPartRowsMinN ? 1u : 0u;
 }
 void note_table_fallback();                // NMX_STAT_TABLE_FALLBACKS (capi.hip)
 void note_scan_timeout();                  // NMX_STAT_SCAN_TIMEOUTS
